@@ -19,9 +19,24 @@ the elapsed time, each rank's verification verdict) goes over gloo on the
 host: the data path has no collective and the bench needs no RCCL.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1MiB|64MiB]
+                       [--dump-outputs DIR] [--full]
   N > 1 without WORLD_SIZE in the environment: this process starts N ranks
   (torch.distributed.run) before touching the GPU and exits with their
   status; under a launcher each rank maps LOCAL_RANK to one device.
+
+A plain run does what the headline figure needs and no more: it builds the
+seeded batch, warms up, times the K steps, writes `--dump-outputs` if asked
+and prints the line (`verified` is null: nothing was checked).  `--full`
+adds, after the timed region, everything else the line can carry: the
+poisoned-decode verification, the host-memory (C ABI) leg, the CPU baselines
+with their parity check against the GPU and the live pattern ceiling of the
+headline kernel (`--no-host`, `--no-cpu`, `--no-ceiling` drop one of them).
+
+`--dump-outputs DIR` writes what the last timed step produced, as float32
+`DIR/parity.npy` (the encode's coding blocks) and `DIR/decoded.npy` (the
+data blocks the decode rebuilt): a fixed seeded sample of DUMP_SAMPLE bytes
+of each, the same positions of the same seeded batch in every run, so two
+builds can be compared output for output (`.rankR` before `.npy` at N > 1).
 """
 import argparse
 import json
@@ -50,6 +65,8 @@ WORKLOADS = {
 # The GPU box grants one GPU's process 16 CPUs (the harness's CPU share);
 # nproc / affinity there show the whole host.  Used when no cgroup quota says.
 BOX_CPU_SHARE = 16
+DUMP_SAMPLE = 4 << 20  # bytes sampled per --dump-outputs array (16 MiB each as float32)
+DUMP_SEED = 0xD0E5
 
 
 def shard_range(rank, world, total):
@@ -72,15 +89,21 @@ def parse(argv=None):
     p.add_argument("--size", type=int, default=None, help="object bytes (default: the workload's)")
     p.add_argument("--oversubscribe", action="store_true",
                    help="allow more ranks than devices (ranks share devices; rehearsal only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a fixed seeded sample of the last step's "
+                        "outputs (parity, rebuilt data blocks) as DIR/<name>.npy, float32")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the verification, the host-memory leg, "
+                        "the CPU baselines and the pattern ceiling (a plain run has none of them)")
     p.add_argument("--cpu-seconds", type=float, default=12.0,
                    help="target CPU time of the bounded cpu_baseline sample")
     p.add_argument("--cpu-objects", type=int, default=1024,
                    help="objects in the cpu_baseline sample (copied from rank 0's batch)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     p.add_argument("--no-ceiling", action="store_true",
-                   help="skip the live access-pattern ceiling of the headline kernel")
+                   help="--full: skip the live access-pattern ceiling of the headline kernel")
     p.add_argument("--no-host", action="store_true",
-                   help="skip the host-memory (C ABI, PCIe-inclusive) leg")
+                   help="--full: skip the host-memory (C ABI, PCIe-inclusive) leg")
     p.add_argument("--host-callers", type=int, default=32,
                    help="caller threads of the host-memory leg (one 1 MiB object each)")
     p.add_argument("--host-seconds", type=float, default=1.0,
@@ -953,6 +976,34 @@ def _poison_decode(be, objs, ref, parity, size, bs, erased):
     return bool(objs.equal(ref))
 
 
+def dump_outputs(outdir, rank, world, objs, parity, size, bs):
+    """--dump-outputs: what the last timed step left, as float32 .npy files:
+    `parity` (the encode's M coding blocks of every object) and `decoded`
+    (the data blocks ERASED that the in-place decode rebuilt).  Each is the
+    bytes at DUMP_SAMPLE positions drawn once from a seeded generator (all of
+    them where the output is smaller), in ascending position order: the same
+    positions for the same batch shape in every run and every build."""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    tag = "" if world == 1 else f".rank{rank}"
+    dec_cols = np.concatenate([np.arange(b * bs, min((b + 1) * bs, size), dtype=np.int64)
+                               for b in ERASED if b < K and b * bs < size])
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    for name, t, cols in (("parity", parity, np.arange(parity.shape[1], dtype=np.int64)),
+                          ("decoded", objs, dec_cols)):
+        total = t.shape[0] * len(cols)
+        if total <= DUMP_SAMPLE:
+            pos = np.arange(total, dtype=np.int64)
+        else:
+            pos = np.sort(rng.integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+        row = torch.from_numpy(pos // len(cols)).to(t.device)
+        col = torch.from_numpy(cols[pos % len(cols)]).to(t.device)
+        vals = t[row, col].to(torch.float32).cpu().numpy()
+        np.save(os.path.join(outdir, f"{name}{tag}.npy"), vals)
+
+
 def run_rank(args, be, rank, world, dist=None):
     """One rank of the bench; returns (record-or-None, verified)."""
     size = args.size or WORKLOADS[args.workload][0]
@@ -973,7 +1024,7 @@ def run_rank(args, be, rank, world, dist=None):
 
     objs = be.random_batch(n, size, 0x1E0E + lo)
     parity = be.empty(n, M * bs)
-    ref = objs.clone()
+    ref = objs.clone() if args.full else None  # the pristine batch, for the checks
 
     def step(ev=None):
         if ev is not None:
@@ -1014,16 +1065,20 @@ def run_rank(args, be, rank, world, dist=None):
     enc_ms = sum(enc_t) / len(enc_t)
     dec_ms = sum(dec_t) / len(dec_t)
 
-    # verification, outside the timed region
-    intact = bool(objs.equal(ref))                       # the timed decodes kept the batch
-    dec_ok = _poison_decode(be, objs, ref, parity, size, bs, ERASED)
-    dec2_ok = _poison_decode(be, objs, ref, parity, size, bs, VERIFY_ERASED)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, objs, parity, size, bs)
+
+    checks = {}
+    if args.full:
+        # verification, outside the timed region
+        checks["timed_batch_intact"] = bool(objs.equal(ref))  # the timed decodes kept the batch
+        checks["poisoned_decode_0_1_2_3"] = _poison_decode(be, objs, ref, parity, size, bs, ERASED)
+        checks["poisoned_decode_4_7_9_10"] = _poison_decode(be, objs, ref, parity, size, bs,
+                                                            VERIFY_ERASED)
     mine = {"rank": rank, "device": getattr(be, "name", "?"), "objects": [lo, hi],
             "elapsed_s": elapsed, "enc_ms": enc_ms, "dec_ms": dec_ms,
-            "warmup_steps": wsteps, "warmup_s": warm_s,
-            "checks": {"timed_batch_intact": intact, "poisoned_decode_0_1_2_3": dec_ok,
-                       "poisoned_decode_4_7_9_10": dec2_ok}}
-    if not args.no_host and hasattr(be, "host_path"):
+            "warmup_steps": wsteps, "warmup_s": warm_s, "checks": checks}
+    if args.full and not args.no_host and hasattr(be, "host_path"):
         # every rank, its own device: the node's host-memory rate at N > 1
         # (parity holds the last timed encode of the pristine batch `ref`)
         try:
@@ -1126,7 +1181,7 @@ def run_rank(args, be, rank, world, dist=None):
             "per_rank": hps}
         verified = verified and all(h["parity_vs_gpu"]["encode_equal"] and
                                     h["parity_vs_gpu"]["decode_equal"] for h in ok)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         # parity holds the last timed encode of the pristine batch (`ref`)
         try:
             cb = cpu_baseline(ref, parity, size, args.cpu_objects, args.cpu_seconds)
@@ -1139,14 +1194,15 @@ def run_rank(args, be, rank, world, dist=None):
         verified = verified and all(c["parity_vs_gpu"]["equal"] for c in checked)
     else:
         rec["cpu_parity_checked"] = False
-    if world == 1 and not args.no_ceiling and hasattr(be, "pattern_ceiling_child"):
+    if args.full and world == 1 and not args.no_ceiling and hasattr(be, "pattern_ceiling_child"):
         # in a child process with the measurement library alone
         try:
             rec["roofline"]["pattern_ceiling"] = be.pattern_ceiling_child(n, size, 0x1E0E + lo)
         except Exception as e:  # never discard the measurement over the ceiling leg
             rec["roofline"]["pattern_ceiling"] = {"achieved": None,
                                                   "error": f"{type(e).__name__}: {e}"}
-    rec["verified"] = verified
+    rec["full"] = bool(args.full)
+    rec["verified"] = verified if args.full else None  # a plain run checks nothing
     return rec, verified
 
 

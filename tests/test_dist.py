@@ -138,7 +138,8 @@ def _run_ranks(world, argv, backend="cpu"):
     return res
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--warmup-s", "0", "--size", "65536"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--warmup-s", "0", "--size", "65536"]
+SMALL = PLAIN + ["--full"]  # the checks and legs after the timed region
 
 
 def test_two_ranks_weak_scaling_through_bench_main():
@@ -310,6 +311,88 @@ def test_single_rank_wrong_parity_fails(monkeypatch):
     rec = json.loads(out.getvalue())
     assert rc == 1 and rec["verified"] is False
     assert rec["cpu_baseline"]["parity_vs_gpu"]["equal"] is False
+
+
+class Spy(WithCeiling):
+    """Counts the device calls and records any leg a plain run must not start."""
+    encodes = decodes = 0
+    legs = []
+
+    def encode(self, objs, size, parity):
+        Spy.encodes += 1
+        super().encode(objs, size, parity)
+
+    def decode(self, objs, size, parity, erased):
+        Spy.decodes += 1
+        super().decode(objs, size, parity, erased)
+
+    def host_path(self, *a, **kw):
+        Spy.legs.append("host")
+        return super().host_path(*a, **kw)
+
+    def pattern_ceiling_child(self, n, size, seed):
+        Spy.legs.append("ceiling")
+        return super().pattern_ceiling_child(n, size, seed)
+
+
+def test_plain_run_times_its_steps_and_nothing_else(monkeypatch):
+    """Without --full the bench warms up, runs exactly --steps timed steps and
+    prints the line: no verification launches, no host, CPU or ceiling leg;
+    `verified` is null and the headline fields keep their meaning."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: Spy.legs.append("cpu"))
+    Spy.encodes = Spy.decodes = 0
+    Spy.legs = []
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        rc = bench.main(["--objects", "4"] + PLAIN, backend=Spy)
+    rec = json.loads(out.getvalue())
+    assert rc == 0 and rec["full"] is False and rec["verified"] is None
+    assert Spy.legs == [] and (Spy.encodes, Spy.decodes) == (1 + 3, 1 + 3)  # warm-up + steps
+    assert rec["steps"] == 3 and rec["warmup_steps_run"] == 1
+    assert rec["cpu_baseline"] is None and "host_path" not in rec
+    assert "pattern_ceiling" not in rec["roofline"] and rec["per_rank"][0]["checks"] == {}
+    assert rec["metric"] == bench.METRIC and rec["unit"] == "GiB/s" and rec["dtype"] == "u8"
+    assert rec["higher_is_better"] is True
+    el = rec["per_rank"][0]["elapsed_s"]
+    assert rec["ms_per_step"] == pytest.approx(el / 3 * 1e3, rel=1e-2, abs=1e-3)
+    assert rec["value"] == pytest.approx(2 * 4 * 65536 * 3 / el / 2**30, rel=2e-2)
+
+
+def test_dump_outputs_holds_the_last_steps_results(monkeypatch, tmp_path):
+    """--dump-outputs writes the timed path's outputs as float32 .npy files:
+    everything where the output is small, equal to the oracle's parity and to
+    the objects' erased data blocks, identical from run to run; a large
+    output is a fixed sample of DUMP_SAMPLE positions in ascending order."""
+    import numpy as np
+    from oracle import oracle as O
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    size, n = 65536 + 7, 3
+    argv = ["--objects", str(n), "--steps", "2", "--warmup", "1", "--warmup-s", "0",
+            "--size", str(size)]
+    outs = []
+    for d in ("a", "b"):
+        with contextlib.redirect_stdout(io.StringIO()):
+            assert bench.main(argv + ["--dump-outputs", str(tmp_path / d)], backend=CpuBackend) == 0
+        outs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert sorted(a) == ["decoded.npy", "parity.npy"]
+    assert all(v.dtype == np.float32 and np.array_equal(v, b[k]) for k, v in a.items())
+    objs = CpuBackend(0, 1).random_batch(n, size, 0x1E0E).numpy()
+    bs = len(O.encode("vandrs", bench.K, bench.M, bench.W, objs[0].tobytes())[0])
+    want_par = np.concatenate([np.frombuffer(b"".join(
+        O.encode("vandrs", bench.K, bench.M, bench.W, objs[o].tobytes())[bench.K:]), dtype=np.uint8)
+        for o in range(n)])
+    assert np.array_equal(a["parity.npy"], want_par.astype(np.float32))
+    assert np.array_equal(a["decoded.npy"], objs[:, :len(bench.ERASED) * bs].reshape(-1))
+    # a larger output: a seeded sample of the same positions every time
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    with contextlib.redirect_stdout(io.StringIO()):
+        assert bench.main(argv + ["--dump-outputs", str(tmp_path / "c")], backend=CpuBackend) == 0
+    rng = np.random.Generator(np.random.PCG64(bench.DUMP_SEED))
+    pos = np.sort(rng.integers(0, want_par.size, 1000, dtype=np.int64))
+    assert np.array_equal(np.load(tmp_path / "c" / "parity.npy"), want_par[pos].astype(np.float32))
+    assert np.load(tmp_path / "c" / "decoded.npy").shape == (1000,)
 
 
 def test_gpus_flag_launches_ranks(monkeypatch):

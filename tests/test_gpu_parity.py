@@ -726,7 +726,7 @@ def test_bench_host_leg_on_the_system_runtime(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LEOEC_LIBRARY")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--objects", "64",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--objects", "64",
                         "--steps", "2", "--warmup", "1", "--warmup-s", "0.1", "--no-cpu",
                         "--no-ceiling", "--host-callers", "8", "--host-seconds", "0.2"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=240)

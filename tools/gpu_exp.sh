@@ -10,11 +10,11 @@ for p in "${PARTS[@]}"; do
   case $p in
     variants) step variants 600 python tools/kvariants.py ${KV_ARGS:-} ;;
     pytest) step pytest 1200 python -m pytest tests -x -q -m gpu ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     suite) step suite 900 python tools/bench_suite.py ${SUITE_ARGS:-} ;;
     e2e) step e2e 600 python tools/e2e_bench.py ;;
-    bench_driver) step bench_driver 600 python bench.py --steps 20 --warmup 5 ;;
-    bench64) step bench64 600 python bench.py --workload 64MiB --no-cpu ;;
+    bench_driver) step bench_driver 600 python bench.py --full --steps 20 --warmup 5 ;;
+    bench64) step bench64 600 python bench.py --full --workload 64MiB --no-cpu ;;
     prof64)
       cd /tmp && export TMPDIR=/tmp
       step prof64_stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof64_csv" -o run -- python "$ROOT/bench.py" --workload 64MiB --no-cpu
