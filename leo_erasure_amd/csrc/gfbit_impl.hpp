@@ -80,7 +80,7 @@ struct GfbkArgs {
   DevShard out[4];
   uint32_t coef[4][kMaxK];
   uint32_t ps;     // packet bytes
-  uint32_t vmin;   // smallest valid length over the inputs
+  uint32_t vmin;   // smallest valid length over the inputs and the outputs
   uint32_t tiles;  // tiles per object (over one packet)
   uint32_t xmap;   // 1: xcd_obj_map
 };
@@ -162,7 +162,8 @@ gfbk_apply(const GfbkArgs a) {
   const uint32_t tile = bid - obj * a.tiles;
   const uint32_t t0 = tile * TB;
   const uint32_t off = t0 + threadIdx.x * 16u;
-  // wave-uniform: the tile lies inside every packet of every input
+  // wave-uniform: the tile lies inside every packet of every input and of
+  // every output (the full tile's stores are unguarded)
   const bool full = t0 + TB <= a.ps && 7ull * a.ps + t0 + TB <= (uint64_t)a.vmin;
   if (full) gfbk_tile<K, LA, WG, MASK, true>(a, obj, off, true);
   else gfbk_tile<K, LA, WG, MASK, false>(a, obj, off, off < a.ps);
@@ -181,6 +182,9 @@ int launch_gfbk_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint
   }
   for (int i = 0; i < 4; ++i) {
     a.out[i] = dev_shard(p.out[r0 + i], o0);
+    // a decode's ragged (or empty) last data block among the outputs: its
+    // tiles past the valid length take the edge path, as when it is an input
+    if (a.out[i].valid < a.vmin) a.vmin = a.out[i].valid;
     for (int j = 0; j < kMaxK; ++j)
       a.coef[i][j] = j < nk ? p.coef[(size_t)(r0 + i) * p.K + j0 + j] : 0u;
   }

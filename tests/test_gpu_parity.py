@@ -327,25 +327,37 @@ def test_cauchy_large_launch_gfbk(gpu, le, oracle, n, size):
     1 MiB (4.11 GB) takes it for encode, decode of 4 data blocks and repair
     of 4 blocks; 2,720 ragged objects (3.99 GB) stay on gfbit_apply.  Encode
     parity against the oracle for objects at both ends and in the middle;
-    decode over poisoned blocks back to the objects; repair against the
+    decode over poisoned blocks back to the objects, of the first four data
+    blocks and of the last four (the ragged block 9 an output: whole rows
+    compared, and a guard row after the last object); repair against the
     encoded blocks."""
     k, m, w, cls = 10, 4, 8, "cauchyrs"
     bs, _ = le.layout(cls, (k, m, w), size)
     stride = (size + 15) // 16 * 16
     g = gpu.Generator(device="cuda")
     g.manual_seed(0x6FB4 + n)
-    objs = gpu.randint(0, 256, (n, stride), dtype=gpu.uint8, device="cuda", generator=g)
+    # the objects are the first n rows; the row after the last is a guard
+    arena = gpu.randint(0, 256, (n + 1, stride), dtype=gpu.uint8, device="cuda", generator=g)
+    objs = arena[:n]
     parity = gpu.full((n, m * bs), 0x5A, dtype=gpu.uint8, device="cuda")
     le.device.encode(cls, (k, m, w), objs, size, parity)
     gpu.cuda.synchronize()
     for o in (0, 1, n // 2, n - 2, n - 1):
         ref = oracle.encode(cls, k, m, w, objs[o, :size].cpu().numpy().tobytes())
         assert parity[o].cpu().numpy().tobytes() == b"".join(ref[k:]), f"object {o}"
-    ref = objs.clone()
+    ref = arena.clone()
     objs[:, :m * bs] = 0xA5
     le.device.decode(cls, (k, m, w), objs, size, parity, list(range(m)))
     gpu.cuda.synchronize()
-    assert gpu.equal(objs[:, :size], ref[:, :size])
+    assert gpu.equal(objs[:, :size], ref[:n, :size])
+    # the last four data blocks erased: block 9 (103,936 of 104,960 B at
+    # 1 MiB) is an output and every survivor is full.  Whole rows, the row
+    # after the last included: nothing past `size` is written (the full-tile
+    # decision of launch_gfbk_t counts the outputs' valid lengths).
+    objs[:, (k - m) * bs:size] = 0xA5
+    le.device.decode(cls, (k, m, w), objs, size, parity, list(range(k - m, k)))
+    gpu.cuda.synchronize()
+    assert gpu.equal(arena, ref)
     del ref
     pad = gpu.zeros((n, k * bs), dtype=gpu.uint8, device="cuda")
     pad[:, :size] = objs[:, :size]

@@ -66,7 +66,9 @@ def test_device_random_sweep(gpu, le, oracle, chunk):
     """Device-resident batches: random object counts, sizes and row strides
     (multiples of 16), encode against the oracle on sampled objects, then an
     in-place decode of a random erasure set of at most m blocks (data blocks
-    poisoned first) restoring every byte of every object."""
+    poisoned first) restoring every byte of every row: the objects, the random
+    bytes between `size` and the row stride, and a guard row on each side of
+    the batch (objs and parity)."""
     rng = random.Random(0xDE71CE + chunk)
     for _ in range(PER_CHUNK):
         cls, k, m, w, size = _draw(rng, oracle)
@@ -75,12 +77,18 @@ def test_device_random_sweep(gpu, le, oracle, chunk):
         bs, _ = le.layout(cls, (k, m, w), size)
         n = rng.randint(1, 24)
         stride = (max(size, k * bs) + 15) // 16 * 16 + 16 * rng.randint(0, 3)
-        host, objs = _batch(gpu, n, size, stride, rng.randrange(1 << 30))
-        objs[:, size:] = 0  # bytes past the object (none are read)
-        ref_objs = objs.clone()
-        parity = gpu.full((n, m * bs), 0x5A, dtype=gpu.uint8, device="cuda")
+        # a guard row on each side; the bytes past the object stay random
+        # (none are read as data, none are written)
+        host, arena = _batch(gpu, n + 2, size, stride, rng.randrange(1 << 30))
+        host, objs = host[1:n + 1], arena[1:n + 1]
+        ref_arena = arena.clone()
+        par_arena = gpu.full((n + 2, m * bs), 0x5A, dtype=gpu.uint8, device="cuda")
+        parity = par_arena[1:n + 1]
         le.device.encode(cls, (k, m, w), objs, size, parity)
         gpu.cuda.synchronize()
+        assert gpu.equal(arena, ref_arena), (case, n)
+        assert bool((par_arena[0] == 0x5A).all()) and bool((par_arena[n + 1] == 0x5A).all()), (case, n)
+        ref_par = par_arena.clone()
         par = parity.cpu().numpy()
         for o in sorted({0, n - 1, rng.randrange(n)}):
             r = oracle.encode(cls, k, m, w, host[o, :size].tobytes())
@@ -91,4 +99,5 @@ def test_device_random_sweep(gpu, le, oracle, chunk):
                 objs[:, e * bs:min((e + 1) * bs, size)] = 0xA5
         le.device.decode(cls, (k, m, w), objs, size, parity, erased)
         gpu.cuda.synchronize()
-        assert gpu.equal(objs[:, :size], ref_objs[:, :size]), (case, erased, n)
+        assert gpu.equal(arena, ref_arena), (case, erased, n)
+        assert gpu.equal(par_arena, ref_par), (case, erased, n)

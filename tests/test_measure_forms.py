@@ -297,6 +297,54 @@ def test_cauchy_16B_forms_batches(gpu, le, oracle, measure, form, env):
         assert gpu.equal(objs, ref), (k, m, size)
 
 
+@pytest.mark.parametrize("env,tile", [
+    ({"LEOEC_GFBK_MIN_MIB": "0"}, 1024),  # the shipped launch_gfbk_t<3,64,false,1>
+    ({"LEOEC_GFBIT_FORM": "5"}, 2048), ({"LEOEC_GFBIT_FORM": "5", "LEOEC_GFBIT_WG": "64"}, 1024),
+    ({"LEOEC_GFBIT_FORM": "5", "LEOEC_GFBIT_WG": "256"}, 4096)],
+    ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()) if isinstance(e, dict) else str(e))
+def test_gfbk_ragged_outputs(gpu, le, oracle, measure, env, tile):
+    """gfbk_apply with ragged blocks among its outputs, at small shapes
+    (LEOEC_GFBK_MIN_MIB=0 sends every cauchyrs(10,4,8) launch of 4 outputs to
+    the shipped launch_gfbk_t<3,64,false,1>; LEOEC_GFBIT_FORM=5: the 128-, 64-
+    and 256-lane forms pick_gfbk() builds from the same template, tiles of
+    2,048 / 1,024 / 4,096 B of every packet).  The guarded-arena harness of
+    test_device_edges.py (gpu_helpers.check_decode / check_encode): every
+    erasure set of edge_erasures, among them the last four data blocks with
+    every survivor full, and the encode, at 173,428 B (bs 17,408, last block
+    16,756 B: the whole tile 1 of packet 7 ends 524 B past it), 1,048,576 B
+    (tile 11 ends 192 B past it), the edge sizes of bs 17,408, and 664,321 B,
+    where a whole 4,096-byte tile crosses the end too; every byte of the objs
+    and parity arenas is compared.  launch_gfbk_t once took its full-tile
+    decision from the inputs' valid lengths alone: erased [6,7,8,9] then
+    stored whole tiles of block 9 over the bytes past `size` and into the
+    next object's row (or the trailing guard row)."""
+    import gpu_helpers as H
+    cfg = ("cauchyrs", 10, 4, 8)
+    for key, v in env.items():
+        measure.setenv(key, v)
+    sizes = [173428, 1048576] + H.edge_sizes(10, 8, 17408) + [H.GFBK_WIDE_SIZE]
+    straddling = []
+    errors = []
+    for size in sizes:
+        case = H.edge_case(le, oracle, cfg, size)
+        if H.gfbk_straddles(case.bs, H.block_valids(10, case.bs, size)[-1], tile):
+            straddling.append(size)
+        for erased in H.edge_erasures(10, 4):
+            err = H.check_decode(gpu, le, case, erased)
+            if err:
+                errors.append(err)
+        err = H.check_encode(gpu, le, case)
+        if err:
+            errors.append(err)
+    # a whole tile of this form's width crosses the end of the last block
+    assert H.GFBK_WIDE_SIZE in straddling, (tile, straddling)
+    if tile <= 2048:
+        assert 173428 in straddling, (tile, straddling)
+    if tile == 1024:
+        assert 1048576 in straddling, (tile, straddling)
+    assert not errors, "\n".join(errors)
+
+
 @pytest.mark.parametrize("tgroup", ["5", "128"])
 def test_gf8_segment_map_forms(gpu, le, oracle, measure, tgroup):
     """gf8 tile map 4 (XCD-interleaved runs of consecutive tiles, shipped for
