@@ -10,6 +10,9 @@
 //        -> INFLIGHT (H2D on the input-copy stream, launches on the slot's
 //                     stream, D2H on the output-copy stream, chained by events)
 //        -> DONE (callers copy their outputs out) -> FREE (last reader).
+// A large batch's output comes back in up to Knobs::hostq_done_groups copies,
+// one per contiguous group of its jobs, and the callers of a group are woken
+// when their copy has landed (Slot::done_groups), not when the last one has.
 // The worker closes the open slot whenever fewer than Knobs::hostq_depth
 // batches are on the GPU, so calls arriving while the GPU is busy pile into
 // one batch, and a lone call is launched at once.  The completer thread waits for batches
@@ -37,6 +40,14 @@ constexpr int kSlots = 5;
 constexpr uint64_t kSlotBytes = (uint64_t)16 << 20;  // input arena (and output arena) per batch
 constexpr size_t kMaxJobs = 256;
 constexpr uint64_t kAlign = 256;
+constexpr int kMaxGroups = 8;  // output groups of a batch (Knobs::hostq_done_groups)
+// Batches with less output than this keep one group.  (LEOEC_HOSTQ_GROUP_MIN_OUT:
+// a smaller bound for the host sanitizer harness, tests/host_sanitize, whose
+// CPU kernels make 1 MiB batches slow.)
+#ifndef LEOEC_HOSTQ_GROUP_MIN_OUT
+#define LEOEC_HOSTQ_GROUP_MIN_OUT ((uint64_t)1 << 20)
+#endif
+constexpr uint64_t kGroupMinOut = LEOEC_HOSTQ_GROUP_MIN_OUT;
 static_assert(kBatchMaxJobBytes <= kSlotBytes, "a batched job must fit one slot");
 
 uint64_t align_up(uint64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
@@ -70,6 +81,8 @@ inline void stat_lane_jobs(int, double) {}
 
 enum class St { kFree, kOpen, kClosed, kInflight, kDone };
 
+std::atomic<long> g_group_batches{0};  // batches launched with more than one output group
+
 struct Slot {
   St state = St::kFree;
   bool ready = false;  // buffers, stream and event exist
@@ -87,10 +100,20 @@ struct Slot {
   hipEvent_t ev_done = nullptr; // the one recorded for this batch (ev or ev_blk)
   hipEvent_t ev_h2d = nullptr;  // after the input copy: the H2D engine is free for the next batch
   hipEvent_t ev_k = nullptr;    // after the launches: the output copy may start
+  hipEvent_t ev_grp[kMaxGroups - 1] = {};      // after the output copy of every group but the
+  hipEvent_t ev_grp_blk[kMaxGroups - 1] = {};  //   last (whose event is ev_done); plain / blocking
   uint64_t used_in = 0, used_out = 0;
   std::vector<const HostJob*> jobs;
   std::vector<uint64_t> in_off, out_off;
   std::vector<int> job_rc;  // per job: its launch's status
+  // Output groups: written by launch_slot, published with the slot's push to
+  // `inflight`; a caller reads them only once done_groups > 0.
+  int groups = 1;                      // groups of this batch (1 .. kMaxGroups)
+  std::vector<uint8_t> job_grp;        // per job: its group
+  hipEvent_t grp_ev[kMaxGroups] = {};  // per group: the event after its copy (nullptr: none
+                                       //   was recorded; the last group's is ev_done)
+  int grp_rc[kMaxGroups] = {};         // per group: its copy's and event's status
+  int done_groups = 0;                 // groups whose outputs are in h_out (under Queue::mu)
   int lane = -1;
   int reserved = 0, filled = 0, readers = 0;
   int status = LEOEC_OK;    // the batch's copies and event: fails every job
@@ -147,6 +170,17 @@ bool wait_h2d_or_closed(hipEvent_t ev, const Queue* q) {
   }
 }
 
+// The events of a slot's output groups (both kinds: Knobs::hostq_sync = 2
+// waits on blocking-sync events).
+bool group_events(Slot* s) {
+  for (int g = 0; g < kMaxGroups - 1; ++g)
+    if (hipEventCreateWithFlags(&s->ev_grp[g], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->ev_grp_blk[g], hipEventDisableTiming | hipEventBlockingSync) !=
+            hipSuccess)
+      return false;
+  return true;
+}
+
 int slot_alloc(Slot* s) {
   if (hipHostMalloc((void**)&s->h_in, kSlotBytes, hipHostMallocMapped) != hipSuccess ||
       hipHostMalloc((void**)&s->h_out, kSlotBytes, hipHostMallocMapped) != hipSuccess ||
@@ -159,7 +193,17 @@ int slot_alloc(Slot* s) {
       hipEventCreateWithFlags(&s->ev_blk, hipEventDisableTiming | hipEventBlockingSync) !=
           hipSuccess ||
       hipEventCreateWithFlags(&s->ev_h2d, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_k, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&s->ev_k, hipEventDisableTiming) != hipSuccess ||
+      !group_events(s)) {
+    for (hipEvent_t* e : {&s->ev, &s->ev_blk, &s->ev_h2d, &s->ev_k}) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
+    }
+    for (int g = 0; g < kMaxGroups - 1; ++g) {
+      if (s->ev_grp[g]) (void)hipEventDestroy(s->ev_grp[g]);
+      if (s->ev_grp_blk[g]) (void)hipEventDestroy(s->ev_grp_blk[g]);
+      s->ev_grp[g] = s->ev_grp_blk[g] = nullptr;
+    }
     if (s->h_in) (void)hipHostFree(s->h_in);
     if (s->h_out) (void)hipHostFree(s->h_out);
     if (s->d_in) (void)hipFree(s->d_in);
@@ -184,7 +228,8 @@ bool same_map(const HostJob& a, const HostJob& b) {
 
 // Enqueue one batch: ONE H2D of the input arena, one launch per run of
 // consecutive identical maps (their regions are uniformly strided: they were
-// reserved back to back with the same sizes), ONE D2H of the output arena.
+// reserved back to back with the same sizes), ONE D2H of the output arena
+// (or one per output group, Knobs::hostq_done_groups).
 // The copies go on the queue's two copy streams (Knobs::hostq_streams = 1,
 // shipped), the launches on the slot's stream after the H2D's event, the
 // D2H after the launches' event: batch b's D2H then runs beside batch b+1's
@@ -253,15 +298,63 @@ int launch_slot(Slot* s) {
       (hipEventRecord(s->ev_k, s->stream) != hipSuccess ||
        hipStreamWaitEvent(cout, s->ev_k, 0) != hipSuccess))
     rc = LEOEC_E_HIP;
-  if (rc == LEOEC_OK && !zc &&
-      hipMemcpyAsync(s->h_out, s->d_out, s->used_out, hipMemcpyDeviceToHost, cout) != hipSuccess)
-    rc = LEOEC_E_HIP;
+  // Output groups (Knobs::hostq_done_groups): the jobs in reservation order,
+  // cut where their output offset crosses a G-th of the batch's output, so a
+  // group is one contiguous range of the output arena.  A batch on the slot's
+  // stream or with little output keeps one group (small batches lose to
+  // extra cross-stream events: Knobs::hostq_split_kib).
+  const bool blk = knobs().hostq_sync == 2;
+  s->ev_done = blk ? s->ev_blk : s->ev;
+  s->job_grp.assign(n, 0);
+  uint64_t g_begin[kMaxGroups + 1] = {};
+  int G = 1;
+  if (split && knobs().hostq_done_groups > 1 && s->used_out >= kGroupMinOut) {
+    const uint64_t want = (uint64_t)std::min(knobs().hostq_done_groups, kMaxGroups);
+    uint64_t share = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t sh = s->out_off[i] * want / s->used_out;
+      if (sh != share) {
+        share = sh;
+        g_begin[G++] = s->out_off[i];
+      }
+      s->job_grp[i] = (uint8_t)(G - 1);
+    }
+  }
+  g_begin[G] = s->used_out;
+  s->groups = G;
+  if (G > 1) g_group_batches.fetch_add(1, std::memory_order_relaxed);
+  for (int g = 0; g < kMaxGroups; ++g) {
+    s->grp_ev[g] = nullptr;
+    s->grp_rc[g] = LEOEC_OK;
+  }
+  // one D2H and one event per group; a copy or an event that fails fails
+  // its group and every later one (their copies are not issued)
+  int bad = rc == LEOEC_OK ? G : 0;  // the first group without its output
+  for (int g = 0; g < G && bad == G && !zc; ++g) {
+    bool fail = false;
+#ifdef LEOEC_MEASURE
+    // fault injection (LEOEC_HOSTQ_FAIL_GROUP): this group's copy "fails"
+    fail = G > 1 && knobs().hostq_fail_group == g;
+#endif
+    fail = fail || hipMemcpyAsync(s->h_out + g_begin[g], s->d_out + g_begin[g],
+                                  g_begin[g + 1] - g_begin[g], hipMemcpyDeviceToHost,
+                                  cout) != hipSuccess;
+    if (!fail && g + 1 < G) {
+      hipEvent_t e = blk ? s->ev_grp_blk[g] : s->ev_grp[g];
+      if (hipEventRecord(e, cout) == hipSuccess)
+        s->grp_ev[g] = e;
+      else
+        fail = true;
+    }
+    if (fail) bad = g;
+  }
+  for (int g = bad; g < G; ++g) s->grp_rc[g] = LEOEC_E_HIP;
   stat_add(13, us_since(t));
-  s->ev_done = knobs().hostq_sync == 2 ? s->ev_blk : s->ev;
   hipStream_t last = cout;
-  if (split && rc != LEOEC_OK) {
+  if (split && bad < G) {
     // a failure part-way: drain whatever this batch enqueued on the three
-    // streams, so the event below (on the slot's stream) follows all of it
+    // streams (every group copy that was issued), so the event below (on the
+    // slot's stream) follows all of it
     (void)hipStreamSynchronize(cin);
     (void)hipStreamSynchronize(s->stream);
     (void)hipStreamSynchronize(cout);
@@ -270,7 +363,7 @@ int launch_slot(Slot* s) {
   if (hipEventRecord(s->ev_done, last) != hipSuccess) {
     (void)hipStreamSynchronize(last);  // no event to wait on: drain here
     if (split) (void)hipStreamSynchronize(s->stream);
-    if (rc == LEOEC_OK) rc = LEOEC_E_HIP;
+    s->grp_rc[G - 1] = LEOEC_E_HIP;
   }
   return rc;
 }
@@ -344,15 +437,28 @@ void completer_main(Queue* q) {
   for (;;) {
     q->cv_complete.wait(lk, [q] { return !q->inflight.empty(); });
     Slot* s = q->inflight.front();
-    lk.unlock();
-    const Clock::time_point tw = Clock::now();
-    const int rc = wait_event(s->ev_done) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
-    stat_add(5, us_since(tw));
-    lk.lock();
+    const int G = s->groups;
+    // the groups' events in order, each group's callers released as its
+    // output lands; a group that failed at launch has no event (its status
+    // is set), and the final event follows everything the batch enqueued
+    bool failed = false;
+    for (int g = 0; g < G; ++g) {
+      hipEvent_t e = g + 1 < G ? s->grp_ev[g] : s->ev_done;
+      lk.unlock();
+      const Clock::time_point tw = Clock::now();
+      if (e && wait_event(e) != hipSuccess) failed = true;  // this group and every later one
+      stat_add(5, us_since(tw));
+      lk.lock();
+      if (failed) s->grp_rc[g] = LEOEC_E_HIP;
+      if (g + 1 == G) break;
+      s->done_groups = g + 1;
+      s->cv_done.notify_all();
+      if (q->done_waiters > 0) q->cv_done.notify_all();
+    }
     s->done = Clock::now();
     q->inflight.pop_front();
     if (q->last == s) q->last = nullptr;
-    if (s->status == LEOEC_OK) s->status = rc;
+    s->done_groups = G;
     s->state = St::kDone;
     s->cv_done.notify_all();  // this batch's callers
     if (q->done_waiters > 0) q->cv_done.notify_all();  // (round-4 form: every caller)
@@ -523,6 +629,18 @@ bool hostq_queue_ready(int dev) {
 
 int hostq_queues_built() { return g_queues_built.load(std::memory_order_relaxed); }
 
+long hostq_group_batches() { return g_group_batches.load(std::memory_order_relaxed); }
+
+int hostq_slots_busy() {
+  int busy = 0;
+  for (LaneQueue& L : g_lane_queue)
+    if (Queue* q = L.q.load(std::memory_order_acquire)) {
+      std::lock_guard<std::mutex> lock(q->mu);
+      for (const Slot& s : q->slots) busy += s.state != St::kFree;
+    }
+  return busy;
+}
+
 int hostq_spread(const int* devices, int n) {
   int rc = device_init();
   if (rc) return rc;
@@ -599,6 +717,8 @@ int hostq_run(const HostJob& job, HostqTicket* ticket, void (*overlap)(void*), v
     f->out_off.clear();
     f->job_rc.clear();
     f->reserved = f->filled = f->readers = 0;
+    f->groups = 1;
+    f->done_groups = 0;
     f->status = LEOEC_OK;
     f->opened = std::chrono::steady_clock::now();
     q->open = f;
@@ -645,15 +765,21 @@ int hostq_run(const HostJob& job, HostqTicket* ticket, void (*overlap)(void*), v
   if (overlap) overlap(arg);
   lk.lock();
   const Clock::time_point tw = Clock::now();
+  // (job_grp is the worker's until the batch is in flight: done_groups > 0
+  // says it is)
+  const auto landed = [s, idx] {
+    return s->state == St::kDone || (s->done_groups > 0 && s->done_groups > (int)s->job_grp[idx]);
+  };
   if (wake) {
-    s->cv_done.wait(lk, [s] { return s->state == St::kDone; });
+    s->cv_done.wait(lk, landed);
   } else {
     ++q->done_waiters;
-    q->cv_done.wait(lk, [s] { return s->state == St::kDone; });
+    q->cv_done.wait(lk, landed);
     --q->done_waiters;
   }
   stat_add(8, us_since(tw));
-  const int status = s->status != LEOEC_OK ? s->status : s->job_rc[idx];
+  const int grc = s->grp_rc[s->job_grp[idx]];
+  const int status = s->status != LEOEC_OK ? s->status : grc != LEOEC_OK ? grc : s->job_rc[idx];
   lk.unlock();
   if (status == LEOEC_OK)
     for (const OutSeg& g : job.out) std::memcpy(g.dst, s->h_out + oo + g.off, g.n);

@@ -93,6 +93,14 @@ void hostq_warm(int dev);
 bool hostq_queue_ready(int dev);
 int hostq_queues_built();
 
+// Batch slots of this process's queues that are not free (tests: no slot
+// leaks; 0 once every call has returned).
+int hostq_slots_busy();
+
+// Batches launched so far whose output came back in more than one group
+// (tests: group-wise completion was exercised).
+long hostq_group_batches();
+
 // leoec_host_spread: spread host-memory calls over these device ordinals
 // (n > 0), or run each on the caller's current device again (n == 0).
 // Returns the number of lanes in the set or a negative status.

@@ -145,6 +145,13 @@ __device__ __forceinline__ u32x4 load_guarded(const uint8_t* p, uint32_t off, ui
   return v;
 }
 
+// The clearing half of load_guarded, for a chunk loaded through shard_rsrc
+// (chunks wholly past `valid` are zeros already).
+__device__ __forceinline__ u32x4 clip_guarded(u32x4 v, uint32_t off, uint32_t valid) {
+  if (off + 16u > valid) v = keep_first(v, off < valid ? valid - off : 0u);
+  return v;
+}
+
 // Guarded store: never writes a byte at or past `valid`.
 __device__ __forceinline__ void store_guarded(uint8_t* p, uint32_t off, uint32_t valid, u32x4 v) {
   if (off + 16u <= valid) {
@@ -364,12 +371,24 @@ __device__ __forceinline__ void gf8_load(const Gf8Args<K, R>& a, uint64_t o, uin
       for (int c = 0; c < CPT; ++c)
         d[c][j] = ld16<NT>(a.in[j].base + o * a.in[j].stride + off + c * kTileBytes);
   } else {
+    // a tile that crosses a valid length: unconditional loads through
+    // shard_rsrc (chunks past `valid` read as zeros without a memory access),
+    // all K issued back to back, and the straddling chunk's tail cleared
+    // afterwards.  (load_guarded's per-lane branch around each load made the
+    // compiler wait for every outstanding load before the next one: the K
+    // loads of an edge tile ran one after another.)
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const auto rs = shard_rsrc(a.in[j].base, a.in[j].stride, a.in[j].valid, o, 16u);
+#pragma unroll
+      for (int c = 0; c < CPT; ++c)
+        d[c][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + c * kTileBytes, 0, 2);
+    }
 #pragma unroll
     for (int j = 0; j < K; ++j)
 #pragma unroll
       for (int c = 0; c < CPT; ++c)
-        d[c][j] = load_guarded(a.in[j].base + o * a.in[j].stride, off + c * kTileBytes,
-                               a.in[j].valid);
+        d[c][j] = clip_guarded(d[c][j], off + c * kTileBytes, a.in[j].valid);
   }
 }
 
@@ -377,15 +396,26 @@ template <int K, int R, bool ACC, int CPT, bool NT, uint32_t CS = kTileBytes>
 __device__ __forceinline__ void gf8_init_store(const Gf8Args<K, R>& a, uint64_t o, uint32_t off,
                                                u32x4 (&acc)[CPT][R]) {
   constexpr uint32_t kTileBytes = CS;
+  if (!ACC) {
 #pragma unroll
-  for (int c = 0; c < CPT; ++c)
+    for (int c = 0; c < CPT; ++c)
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      acc[c][r] = u32x4{0u, 0u, 0u, 0u};
-      if (ACC)
-        acc[c][r] = load_guarded(a.out[r].base + o * a.out[r].stride, off + c * kTileBytes,
-                                 a.out[r].valid);
-    }
+      for (int r = 0; r < R; ++r) acc[c][r] = u32x4{0u, 0u, 0u, 0u};
+    return;
+  }
+  // the running outputs, loaded as gf8_load's guarded tiles are
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const auto rs = shard_rsrc(a.out[r].base, a.out[r].stride, a.out[r].valid, o, 16u);
+#pragma unroll
+    for (int c = 0; c < CPT; ++c)
+      acc[c][r] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + c * kTileBytes, 0, 2);
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int c = 0; c < CPT; ++c)
+      acc[c][r] = clip_guarded(acc[c][r], off + c * kTileBytes, a.out[r].valid);
 }
 
 template <int K, int R, int CPT, bool NT, uint32_t CS = kTileBytes, bool BUF = false>
@@ -408,12 +438,26 @@ __device__ __forceinline__ void gf8_store(const Gf8Args<K, R>& a, uint64_t o, ui
         st16<NT>(const_cast<uint8_t*>(a.out[r].base) + o * a.out[r].stride + off + c * kTileBytes,
                  acc[c][r]);
   } else {
+    // whole chunks through a resource that ends at the last whole chunk of
+    // `valid` (the hardware drops the chunks past it: no branch around a
+    // store); the one lane whose chunk straddles `valid` writes its bytes
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint32_t valid = a.out[r].valid;
+      const auto rs = shard_rsrc(a.out[r].base, a.out[r].stride, valid & ~15u, o, 16u);
+#pragma unroll
+      for (int c = 0; c < CPT; ++c)
+        __builtin_amdgcn_raw_buffer_store_b128(acc[c][r], rs, off + c * kTileBytes, 0, 2);
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r)
 #pragma unroll
-      for (int c = 0; c < CPT; ++c)
-        store_guarded(const_cast<uint8_t*>(a.out[r].base) + o * a.out[r].stride,
-                      off + c * kTileBytes, a.out[r].valid, acc[c][r]);
+      for (int c = 0; c < CPT; ++c) {
+        const uint32_t p = off + c * kTileBytes, valid = a.out[r].valid;
+        if (p < valid && p + 16u > valid)
+          store_guarded(const_cast<uint8_t*>(a.out[r].base) + o * a.out[r].stride, p, valid,
+                        acc[c][r]);
+      }
   }
 }
 

@@ -81,6 +81,10 @@ const Knobs* read_env() {
   k->hostq_survivors = env_int("LEOEC_HOSTQ_SURVIVORS", k->hostq_survivors);
   k->hostq_wake = env_int("LEOEC_HOSTQ_WAKE", k->hostq_wake);
   k->hostq_fail_bs = env_int("LEOEC_HOSTQ_FAIL_BS", k->hostq_fail_bs);
+  k->hostq_done_groups = env_int("LEOEC_HOSTQ_DONE_GROUPS", k->hostq_done_groups);
+  if (k->hostq_done_groups != 2 && k->hostq_done_groups != 4 && k->hostq_done_groups != 8)
+    k->hostq_done_groups = 1;
+  k->hostq_fail_group = env_int("LEOEC_HOSTQ_FAIL_GROUP", k->hostq_fail_group);
   k->gf8_variant = env_int("LEOEC_GF8_VARIANT", k->gf8_variant);
   k->gf8_tmap = env_int("LEOEC_GF8_TMAP", k->gf8_tmap);
   k->gf8_tmap_set = lookup("LEOEC_GF8_TMAP") != nullptr;

@@ -51,6 +51,14 @@ struct Knobs {
                              //   unchanged; profiles/r05_s26_*.log, three rotated rounds)
   int hostq_fail_bs = 0;     // LEOEC_HOSTQ_FAIL_BS: batched launches of this block size report
                              //   a HIP error (fault injection: per-job status)
+  int hostq_done_groups = 1; // LEOEC_HOSTQ_DONE_GROUPS: 1, 2, 4 or 8: a batch on the copy streams
+                             //   with at least 1 MiB of output brings it back in this many
+                             //   copies, one per contiguous group of its jobs, and wakes each
+                             //   group's callers when its copy has landed (1: one copy, every
+                             //   caller woken after the last byte)
+  int hostq_fail_group = -1; // LEOEC_HOSTQ_FAIL_GROUP: the output copy of this group of every
+                             //   batch with more than one "fails" (fault injection: that group
+                             //   and every later one report a HIP error)
   int hostq_zc = 0;          // LEOEC_HOSTQ_ZC=1: batches without DMA copies (kernels on the
                              //   pinned, device-mapped arenas)
   int hostq_lanes = 0;       // LEOEC_HOSTQ_LANES: dispatcher lanes (0: one per gfx950 device;

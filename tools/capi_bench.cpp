@@ -19,6 +19,7 @@
 //   tools/capi_bench <libleoec*.so> sizes    [K=V,...]   callers() at 16 KiB - 4 MiB
 //                                                        objects, 8 and 32 threads
 //   tools/capi_bench <libleoec*.so> many     [K=V,...]   callers() from 32 - 96 threads
+//   tools/capi_bench <libleoec*.so> groups   [K=V,...]   callers() from 16, 32, 48 threads
 //   tools/capi_bench <libleoec*.so> trace32  [K=V,...]   callers() from 32 threads,
 //                                                        encode then decode (copy trace)
 // K=V: measurement-build knobs (leoec_measure_set_knob), applied after load.
@@ -334,6 +335,10 @@ int main(int argc, char** argv) {
   } else if (mode == "c32") {
     // 32 callers, encode then decode (the bench host leg's concurrency; A/B)
     for (bool dec : {false, true}) callers(32, dec);
+  } else if (mode == "groups") {
+    // 16, 32 and 48 callers, encode then decode (Knobs::hostq_done_groups A/B)
+    for (bool dec : {false, true})
+      for (int T : {16, 32, 48}) callers(T, dec);
   } else if (mode == "many") {
     // 32, 48, 64, 96 callers: whether more callers' packing overlaps the
     // link's idle gaps (round 6: at 32 the next batch's last packs end after
