@@ -145,6 +145,31 @@ int leoec_repair_dev(int coding, int k, int m, int w, const uint8_t *const *bloc
                      const int *repair_ids, int nrepair, uint8_t *const *out,
                      uint64_t out_stride, void *stream);
 
+/* Workspace bytes leoec_verify_dev wants for this batch: 0 where the check is
+ * fused into one kernel (vandrs w = 8 and isars with k <= 16, m <= 4);
+ * otherwise nobj * m * block_size (one pass).  Needs no device. */
+int leoec_verify_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                               uint64_t *bytes);
+
+/* Check nobj stripes laid out as for leoec_encode_dev / leoec_decode_dev.
+ * flags[o] (device, 4-byte aligned, nobj words, every one overwritten) gets
+ * bit i set iff coding block i of object o differs from the encoding of the
+ * object's data anywhere in its block_size bytes; 0 = consistent.  For
+ * m > 32, bit 31 stands for every coding block >= 31.  Data bytes past
+ * `size` are read as zero, as in encode.  objs and parity are never written.
+ * workspace: device, 16-byte aligned; may be NULL when the query returns 0;
+ * otherwise at least m * block_size bytes (one object).  A smaller workspace
+ * than the query's makes the call work through the batch in chunks of
+ * objects on the same stream.
+ * Reading a flag word: every code here is MDS, so one damaged data block
+ * changes every coding block of its encoding and sets every bit 0..m-1,
+ * while one damaged coding block sets only its own bit.
+ * The first verify on a device loads its own code object (1-2 ms); the
+ * leoec_gf_init warm-up does not cover it. */
+int leoec_verify_dev(int coding, int k, int m, int w, const uint8_t *objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
+                     uint32_t *flags, void *workspace, uint64_t workspace_bytes, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
 
 /* Coding matrix the engine uses: m*k words (GF classes) or a (m*w) x (k*w)

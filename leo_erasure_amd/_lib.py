@@ -42,7 +42,7 @@ EXPORTS = (
     "leoec_strerror", "leoec_gf_init", "leoec_check_params", "leoec_layout", "leoec_encode",
     "leoec_decode", "leoec_repair", "leoec_encode_dev", "leoec_decode_dev", "leoec_repair_dev",
     "leoec_coding_matrix", "leoec_device", "leoec_host_lanes", "leoec_host_spread",
-    "leoec_version",
+    "leoec_version", "leoec_verify_dev_workspace", "leoec_verify_dev",
 )
 
 
@@ -91,6 +91,8 @@ def _load(path=LIB_PATH):
                                                  u64, vp]
     L.leoec_coding_matrix.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int,
                                                     ctypes.POINTER(c_int)]
+    L.leoec_verify_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
+    L.leoec_verify_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

@@ -115,6 +115,7 @@ const Knobs* read_env() {
   k->gfbit_cbm = env_int("LEOEC_GFBIT_CBM", k->gfbit_cbm);
   k->gfs_mode = env_int("LEOEC_GFS_MODE", k->gfs_mode);
   k->gfs_pf = env_int("LEOEC_GFS_PF", k->gfs_pf);
+  k->verify_form = env_int("LEOEC_VERIFY_FORM", k->verify_form);
   return k;
 }
 

@@ -116,6 +116,10 @@ struct Knobs {
                              //   bytes take gfbk_apply (w = 8, K = 10, 4 rows; -1: the shipped
                              //   kGfbkMinBytes, gfbit_impl.hpp; a huge value: never)
   int gfbit_form = 0;        // LEOEC_GFBIT_FORM: 0 gfbit_apply (shipped), 1 gfb2_apply (buffer loads)
+  // verify.hip
+  int verify_form = 0;       // LEOEC_VERIFY_FORM=1: leoec_verify_dev always two-pass (encode into
+                             //   the workspace, then compare), also where gf8_check would serve;
+                             //   2: gf8_check<10,4> under gf8_apply's 5-wave register budget
 };
 
 const Knobs& knobs();

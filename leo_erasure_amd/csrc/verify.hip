@@ -1,0 +1,190 @@
+// verify.hip — leoec_verify_dev: do the k data blocks and the m stored coding
+// blocks of every object of a device batch still agree?  One flag word per
+// object, bit i set when coding block i differs from the encoding of the data.
+//
+// Two paths:
+//   fused     GF(2^8) matrix codes with k <= 16, m <= 4 (vandrs w = 8, isars):
+//             gf8_check (verify_impl.hpp) reads the k + m blocks once and
+//             writes nothing for a clean stripe; no workspace;
+//   two-pass  everything else: the ordinary encode plan into the caller's
+//             workspace, then verify_compare against the stored blocks, a
+//             chunk of objects at a time in stream order.
+// This unit is kept out of engine.cpp / capi.cpp: the host sanitizer harness
+// (tests/host_sanitize) links those against stand-in kernels and a stand-in
+// HIP header that know nothing of these launches.  For the same reason the
+// gf_init warm-up does not load this unit's kernels.
+#include <new>
+#include <utility>
+
+#include "engine.hpp"
+#include "knobs.hpp"
+#include "verify_impl.hpp"
+
+namespace leoec {
+
+using namespace detail;
+
+namespace detail {
+int verify_form_env() { return knobs().verify_form; }
+}  // namespace detail
+
+namespace {
+
+template <std::size_t... I>
+CheckFn gf8_check_pick(std::index_sequence<I...>, int k, int r) {
+  static CheckFn (*const sel[])(int) = {&gf8_check_launcher<(int)I + 1>...};
+  return sel[k - 1](r);
+}
+
+// The configurations gf8_check serves: the classes whose plans are
+// Plan::kGf (a GF(2^w) coding matrix), at w = 8, within one launch's K x R.
+// LEOEC_VERIFY_FORM=1 (measurement build): always two-pass.
+bool verify_fused(int coding, int k, int m, int w) {
+  if (kMeasureBuild && knobs().verify_form == 1) return false;
+  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && w == 8 && k <= kMaxK && m <= kMaxR;
+}
+
+// Workspace row (obj, i) = the freshly encoded coding block i of the chunk's
+// object obj, rows packed at bs bytes; one 16-byte column per lane, 4 KiB of
+// a block per workgroup.  A wave in which any column differs ORs the block's
+// bit into the object's flag word (vector atomic); equal blocks write nothing.
+__global__ void __launch_bounds__(kThreads)
+verify_compare(const uint8_t* __restrict__ ws, const uint8_t* __restrict__ parity,
+               uint64_t parity_stride, uint32_t bs, uint32_t m, uint32_t tiles,
+               uint32_t* __restrict__ flags) {
+  const uint32_t row = blockIdx.x / tiles;
+  const uint32_t tile = blockIdx.x - row * tiles;
+  const uint32_t obj = row / m;
+  const uint32_t i = row - obj * m;
+  const uint32_t off = tile * kTileBytes + threadIdx.x * 16u;
+  uint32_t nz = 0;
+  if (off < bs) {  // bs is a multiple of 16: the column lies inside the block
+    const u32x4 x = ld16<false>(ws + (uint64_t)row * bs + off);
+    const u32x4 y = ld16<true>(parity + (uint64_t)obj * parity_stride + (uint64_t)i * bs + off);
+    nz = (x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2]) | (x[3] ^ y[3]);
+  }
+  const bool any = __builtin_amdgcn_ballot_w64(nz != 0u) != 0ull;
+  if (any && (threadIdx.x & 63u) == 0u) atomicOr(&flags[obj], 1u << (i < 31u ? i : 31u));
+}
+
+int op_verify_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                            uint64_t* bytes) {
+  uint64_t bs;
+  const int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  uint64_t per, all;
+  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
+    return LEOEC_E_BAD_SIZE;
+  *bytes = verify_fused(coding, k, m, w) ? 0 : all;
+  return LEOEC_OK;
+}
+
+int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                  uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                  uint32_t* flags, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+  uint64_t bs;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if (nobj == 0 || bs == 0) return LEOEC_OK;
+  if (!objs || !parity || !flags || ((uintptr_t)flags & 3u)) return LEOEC_E_ARG;
+  if (((uintptr_t)objs & 15u) || ((uintptr_t)parity & 15u) || (obj_stride & 15u) ||
+      (parity_stride & 15u))
+    return LEOEC_E_ARG;
+  uint64_t per;  // workspace bytes of one object
+  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || bs >= (1ull << 32)) return LEOEC_E_BAD_SIZE;
+  if (obj_stride < size || parity_stride < per) return LEOEC_E_ARG;
+  const bool fused = verify_fused(coding, k, m, w);
+  if (!fused && (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per))
+    return LEOEC_E_ARG;
+  if ((rc = device_init())) return rc;
+  const Code* c;
+  if ((rc = get_code(coding, k, m, w, &c))) return rc;
+  std::vector<Shard> in(k), par(m);
+  std::vector<int> surv(k), want(m);
+  for (int j = 0; j < k; ++j) {
+    const uint64_t start = (uint64_t)j * bs;
+    in[j] = Shard{objs + start, obj_stride, size <= start ? 0 : (size - start < bs ? size - start : bs)};
+    surv[j] = j;
+  }
+  for (int i = 0; i < m; ++i) {
+    par[i] = Shard{parity + (uint64_t)i * bs, parity_stride, bs};
+    want[i] = k + i;
+  }
+  std::shared_ptr<const Plan> plan;
+  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  if (hipMemsetAsync(flags, 0, nobj * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+  if (fused) {
+    if (plan->kind != Plan::kGf) return LEOEC_E_UNSUPPORTED;
+    GfApply a;
+    a.w = w;
+    a.K = k;
+    a.R = m;
+    a.coef = plan->coef;
+    a.in = in;
+    a.out = par;
+    a.block_size = bs;
+    a.nobj = nobj;
+    const CheckFn fn = gf8_check_pick(std::make_index_sequence<kMaxK>{}, k, m);
+    // as launch(GfApply): no grid above 2^31 - 1 workgroups at the narrowest tiles
+    const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((bs + 1023) / 1024);
+    for (uint64_t o0 = 0; o0 < nobj; o0 += max_obj) {
+      const uint64_t no = nobj - o0 < max_obj ? nobj - o0 : max_obj;
+      if ((rc = fn(a, o0, no, flags, s))) return rc;
+    }
+    return LEOEC_OK;
+  }
+  const uint32_t tiles = (uint32_t)((bs + kTileBytes - 1) / kTileBytes);
+  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
+  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((uint64_t)m * tiles);
+  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
+  if (chunk > max_obj) chunk = max_obj;
+  uint8_t* const ws = static_cast<uint8_t*>(workspace);
+  std::vector<Shard> enc(m);
+  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
+  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
+    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
+    std::vector<Shard> cin(in);
+    for (Shard& sh : cin) sh.base += o0 * obj_stride;
+    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
+    hipLaunchKernelGGL(verify_compare, dim3((uint32_t)(no * m * tiles)), dim3(kThreads), 0, s, ws,
+                       parity + o0 * parity_stride, parity_stride, (uint32_t)bs, (uint32_t)m, tiles,
+                       flags + o0);
+    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+  }
+  return LEOEC_OK;
+}
+
+template <typename F>
+int guarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return LEOEC_E_NOMEM;
+  } catch (...) {
+    return LEOEC_E_ARG;
+  }
+}
+
+}  // namespace
+}  // namespace leoec
+
+extern "C" {
+
+int leoec_verify_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                               uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_verify_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                     uint32_t* flags, void* workspace, uint64_t workspace_bytes, void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_verify_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                parity_stride, flags, workspace, workspace_bytes,
+                                (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"

@@ -74,6 +74,55 @@ def decode(coding, params, objs, size, parity, erased, nobj=None, stream=None):
                                     len(erased), _stream(stream)))
 
 
+VERIFY_WORKSPACE_CAP = 256 << 20  # bytes verify() allocates at most (the batch then goes in chunks)
+
+
+def verify_workspace(coding, params, size, nobj):
+    """leoec_verify_dev_workspace: bytes of workspace verify() wants for one
+    pass over the batch; 0 where the check is fused into one kernel."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_verify_dev_workspace(_cid(coding), k, m, w, size, nobj, ctypes.byref(out)))
+    return out.value
+
+
+def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=None, stream=None):
+    """leoec_verify_dev: one int32 flag word per object, bit i set when the
+    stored coding block i differs from the encoding of the object's data
+    (0: the stripe is consistent).  ``flags`` (int32, ``nobj`` words) and
+    ``workspace`` (uint8) are allocated when not given; a call on an explicit
+    ``stream`` that needs a workspace must be given one, because the caching
+    allocator orders a buffer's reuse only on the stream it knows about."""
+    k, m, w = params
+    nobj = objs.shape[0] if nobj is None else nobj
+    bs, _ = layout(coding, params, size)
+    _rows(objs, nobj, size, "objs")
+    _rows(parity, nobj, m * bs, "parity")
+    if flags is None:
+        flags = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    if flags.dtype != torch.int32 or not flags.is_cuda or flags.dim() != 1 or (
+            flags.numel() > 1 and flags.stride(0) != 1):
+        raise ValueError("flags: contiguous 1-D int32 device tensor expected")
+    if flags.numel() < nobj:
+        raise ValueError(f"flags: {flags.numel()} words, {nobj} needed")
+    need = verify_workspace(coding, params, size, nobj)
+    if need and workspace is None:
+        if stream is not None:
+            raise ValueError("verify on an explicit stream needs an explicit workspace "
+                             f"({need} B for one pass, at least {m * bs} B)")
+        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
+                                device=objs.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError("workspace: contiguous uint8 device tensor expected")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    _lib.check(lib.leoec_verify_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                    nobj, parity.data_ptr(), _row_stride(parity), flags.data_ptr(),
+                                    ws_ptr, ws_bytes, _stream(stream)))
+    return flags
+
+
 def repair(coding, params, blocks, block_size, repair_ids, out, nobj, stream=None):
     """leoec_repair_dev.  ``blocks``: list of k+m tensors-or-None, each
     ``[nobj, stride]`` with the block at byte 0 of every row (all the same
