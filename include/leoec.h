@@ -170,7 +170,53 @@ int leoec_verify_dev(int coding, int k, int m, int w, const uint8_t *objs, uint6
                      uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
                      uint32_t *flags, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* Rebuild, in place, the blocks each object of a batch has lost; every object
+ * has its own set.  The layout is that of leoec_encode_dev / leoec_decode_dev.
+ * lost and unhealed: device, 4-byte aligned, nobj words each, not aliased
+ * (lost == unhealed: LEOEC_E_ARG); k + m <= 32 (else LEOEC_E_UNSUPPORTED).
+ * Bit b of lost[o] (0 <= b < k+m) says block b of object o is lost: ids below
+ * k are data blocks in objs, the rest coding blocks in parity.  The present
+ * contents of a lost block are never read.
+ * An object with at most m bits set and none at or above k+m has every lost
+ * block, coding blocks included, rebuilt from its first k intact ids
+ * ascending (leoec_decode_dev's survivors); data blocks are clipped to
+ * `size` (bytes past it are read as zero and never touched), and unhealed[o]
+ * becomes 0.  Any other object is unrecoverable: nothing of it is written and
+ * unhealed[o] = lost[o].  An object with lost[o] == 0 is neither read nor
+ * written.  Every word of unhealed is overwritten; lost is never written.
+ * vandrs w = 8 and isars with k <= 16, m <= 4 take one launch over the whole
+ * batch and never synchronise; the survivors, outputs and coefficient tables
+ * of every mask of 1..m bits come from a table of the code kept on the device
+ * (1.2 MB at (10,4), 8 MB at (16,4)).  The first heal of a code on a device
+ * builds and uploads that table with a blocking copy (milliseconds; 6,195
+ * 16 x 16 inversions at (16,4)) and loads this call's code object (1-2 ms),
+ * so it belongs outside a stream capture; the leoec_gf_init warm-up covers
+ * neither.  At most 16 tables are kept per process and none is ever freed;
+ * a 17th (code, device) pair is served as the classes below.
+ * Every other class (cauchyrs, liberation, vandrs w = 16 / 32, w = 8 with
+ * k > 16 or m > 4) copies the masks back on `stream` and waits for that copy:
+ * there the call synchronises the stream once and cannot be captured into a
+ * graph; it then enqueues one launch per run of consecutive objects with the
+ * same mask and fills unhealed from the host. */
+int leoec_heal_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                   uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                   const uint32_t *lost, uint32_t *unhealed, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
+
+/* The map leoec_heal_dev uses for one mask of lost ids; needs no device.
+ * surv[0..k): the survivor ids; want[0..*nwant): the lost ids ascending;
+ * coef (may be NULL; cap >= *nwant * k words): row r holds the GF(2^w)
+ * coefficients that give block want[r] from the survivor blocks in surv's
+ * order (liberation has no such matrix: LEOEC_E_UNSUPPORTED when coef is
+ * given).  *index (may be NULL): the mask's record in the device table of the
+ * one-launch configurations (its combinatorial rank: masks of fewer bits
+ * first, then sum over the set bits b_1 < b_2 < ... of C(b_i, i)); -1 for
+ * every other configuration and for mask 0.
+ * A bit at or above k+m: LEOEC_E_BAD_ID; more than m bits:
+ * LEOEC_E_NOT_ENOUGH_BLOCKS; k + m > 32: LEOEC_E_UNSUPPORTED. */
+int leoec_heal_rows(int coding, int k, int m, int w, uint32_t lost_mask, int *surv, int *want,
+                    int *nwant, uint32_t *coef, int cap, int *index);
 
 /* Coding matrix the engine uses: m*k words (GF classes) or a (m*w) x (k*w)
  * 0/1 bitmatrix as bytes (cauchyrs, liberation).  *n_out = entries written. */

@@ -116,6 +116,7 @@ const Knobs* read_env() {
   k->gfs_mode = env_int("LEOEC_GFS_MODE", k->gfs_mode);
   k->gfs_pf = env_int("LEOEC_GFS_PF", k->gfs_pf);
   k->verify_form = env_int("LEOEC_VERIFY_FORM", k->verify_form);
+  k->heal_form = env_int("LEOEC_HEAL_FORM", k->heal_form);
   return k;
 }
 

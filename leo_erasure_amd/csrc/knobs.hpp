@@ -120,6 +120,10 @@ struct Knobs {
   int verify_form = 0;       // LEOEC_VERIFY_FORM=1: leoec_verify_dev always two-pass (encode into
                              //   the workspace, then compare), also where gf8_check would serve;
                              //   2: gf8_check<10,4> under gf8_apply's 5-wave register budget
+  // heal.hip
+  int heal_form = 0;         // LEOEC_HEAL_FORM=1: leoec_heal_dev always through the generic path
+                             //   (masks copied back, one plan launch per run of equal masks),
+                             //   also where gf8_heal would serve
 };
 
 const Knobs& knobs();

@@ -123,6 +123,55 @@ def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=
     return flags
 
 
+def _words(t, nobj, what):
+    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or (
+            t.numel() > 1 and t.stride(0) != 1):
+        raise ValueError(f"{what}: contiguous 1-D int32 device tensor expected")
+    if t.numel() < nobj:
+        raise ValueError(f"{what}: {t.numel()} words, {nobj} needed")
+
+
+def heal(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, stream=None):
+    """leoec_heal_dev: rebuild in place the blocks every object has lost.
+    Bit b of ``lost[o]`` (int32, ``nobj`` words) says block b of object o is
+    lost: ids below k are data blocks in ``objs``, the rest coding blocks in
+    ``parity``.  Returns ``unhealed`` (int32, ``nobj`` words, allocated when
+    not given): 0 for a healed or clean object, ``lost[o]`` for one that
+    cannot be recovered (more than m bits, or a bit at or above k + m), of
+    which nothing is written."""
+    k, m, w = params
+    nobj = objs.shape[0] if nobj is None else nobj
+    bs, _ = layout(coding, params, size)
+    _rows(objs, nobj, size, "objs")
+    _rows(parity, nobj, m * bs, "parity")
+    if unhealed is None:
+        unhealed = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    _words(lost, nobj, "lost")
+    _words(unhealed, nobj, "unhealed")
+    _lib.check(lib.leoec_heal_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                  nobj, parity.data_ptr(), _row_stride(parity), lost.data_ptr(),
+                                  unhealed.data_ptr(), _stream(stream)))
+    return unhealed
+
+
+def heal_rows(coding, params, mask, coef=True):
+    """leoec_heal_rows (no device needed): what heal() does for one mask of
+    lost ids: ``(surv, want, rows, index)`` with the k survivor ids, the lost
+    ids ascending, one list of k GF(2^w) coefficients per lost id (None with
+    ``coef=False``) and the mask's record in the device table (-1 where the
+    configuration has none)."""
+    k, m, w = params
+    surv, want = (ctypes.c_int * k)(), (ctypes.c_int * max(m, 1))()
+    nwant, index = ctypes.c_int(0), ctypes.c_int(-1)
+    cap = m * k
+    rows = (ctypes.c_uint32 * max(cap, 1))() if coef else None
+    _lib.check(lib.leoec_heal_rows(_cid(coding), k, m, w, mask, surv, want, ctypes.byref(nwant),
+                                   rows, cap, ctypes.byref(index)))
+    n = nwant.value
+    return (list(surv), list(want[:n]),
+            [list(rows[r * k:(r + 1) * k]) for r in range(n)] if coef else None, index.value)
+
+
 def repair(coding, params, blocks, block_size, repair_ids, out, nobj, stream=None):
     """leoec_repair_dev.  ``blocks``: list of k+m tensors-or-None, each
     ``[nobj, stride]`` with the block at byte 0 of every row (all the same
