@@ -202,7 +202,56 @@ int leoec_heal_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_
                    uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
                    const uint32_t *lost, uint32_t *unhealed, void *stream);
 
+/* leoec_locate_dev's word for an object that is inconsistent in a way no
+ * single block explains.  The bit lies at or above k + m, so leoec_heal_dev
+ * takes the object for unrecoverable. */
+#define LEOEC_LOCATE_MANY 0x80000000u
+
+/* Name the one damaged block of every object of a batch: the step between
+ * leoec_verify_dev and leoec_heal_dev.  Layout, alignment, stride rules and
+ * the reading of bytes past `size` are those of leoec_verify_dev; objs and
+ * parity are never written.  lost: device, 4-byte aligned, nobj words, every
+ * one overwritten:
+ *   0                  the stripe is consistent;
+ *   one bit b < k + m  block b is the only block whose replacement makes the
+ *                      stripe consistent (leoec_heal_dev's ids: below k data,
+ *                      the rest coding);
+ *   LEOEC_LOCATE_MANY  the stripe is inconsistent and no single block explains
+ *                      it.
+ * The words go into leoec_heal_dev as its `lost` as they are: a
+ * LEOEC_LOCATE_MANY object is left alone and comes back in `unhealed`.
+ * Served: vandrs w = 8 and isars with k <= 16 and 2 <= m <= 4.  Everything
+ * else (m = 1, k > 16, m > 4, vandrs w = 16 / 32, cauchyrs, liberation) is
+ * LEOEC_E_UNSUPPORTED, returned before the device is opened; invalid
+ * parameters keep their leoec_check_params status; nobj == 0 is LEOEC_OK.
+ * How it tells: per byte column the syndromes s_i = stored coding block i ^
+ * encoding of the data are all zero (clean), non-zero in one i only (coding
+ * block i), or s_i = C[i][j] / C[0][j] * s_0 for every i (data block j); an
+ * object's answer is the block that fits every column.  That is unique
+ * because no entry and no 2 x 2 minor of the coding matrix C is zero, which
+ * every call checks (leoec_locate_rows).
+ * The limit at m = 2: two parity blocks can name one damaged block or detect
+ * two, not both.  With m >= 3 two damaged blocks are never taken for one
+ * (LEOEC_LOCATE_MANY); with m = 2 they may be reported as a third block, and
+ * healing that block then leaves a consistent but wrong stripe.
+ * The call allocates nothing, uploads nothing and never synchronises: a
+ * memset and two launches on `stream`, so it can be captured into a graph.
+ * The first locate on a device loads its own code object (1-2 ms); the
+ * leoec_gf_init warm-up does not cover it. */
+int leoec_locate_dev(int coding, int k, int m, int w, const uint8_t *objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
+                     uint32_t *lost, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
+
+/* The ratios leoec_locate_dev tests the syndromes with; needs no device.
+ * ratio (cap >= (m-1) * k words): row i-1 holds T[i][0..k) = C[i][j] / C[0][j]
+ * in GF(2^8), i = 1..m-1, C being leoec_coding_matrix's.  ratio == NULL or
+ * cap too small: LEOEC_E_ARG.  Configurations leoec_locate_dev does not serve
+ * get its statuses.  While building T the two properties the answer's
+ * uniqueness rests on are checked (no zero entry, no singular 2 x 2 minor of
+ * C): LEOEC_E_UNSUPPORTED if either fails. */
+int leoec_locate_rows(int coding, int k, int m, int w, uint32_t *ratio, int cap);
 
 /* The map leoec_heal_dev uses for one mask of lost ids; needs no device.
  * surv[0..k): the survivor ids; want[0..*nwant): the lost ids ascending;

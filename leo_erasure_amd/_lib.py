@@ -43,7 +43,7 @@ EXPORTS = (
     "leoec_decode", "leoec_repair", "leoec_encode_dev", "leoec_decode_dev", "leoec_repair_dev",
     "leoec_coding_matrix", "leoec_device", "leoec_host_lanes", "leoec_host_spread",
     "leoec_version", "leoec_verify_dev_workspace", "leoec_verify_dev", "leoec_heal_dev",
-    "leoec_heal_rows",
+    "leoec_heal_rows", "leoec_locate_dev", "leoec_locate_rows",
 )
 
 
@@ -99,6 +99,8 @@ def _load(path=LIB_PATH):
                                                 ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                                 ctypes.POINTER(ctypes.c_uint32), c_int,
                                                 ctypes.POINTER(c_int)]
+    L.leoec_locate_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp]
+    L.leoec_locate_rows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

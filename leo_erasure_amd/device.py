@@ -172,6 +172,41 @@ def heal_rows(coding, params, mask, coef=True):
             [list(rows[r * k:(r + 1) * k]) for r in range(n)] if coef else None, index.value)
 
 
+LOCATE_MANY = 0x80000000  # LEOEC_LOCATE_MANY: inconsistent, and no single block explains it
+
+
+def locate(coding, params, objs, size, parity, nobj=None, lost=None, stream=None):
+    """leoec_locate_dev: one int32 word per object naming its one damaged
+    block: 0 for a consistent stripe, bit b (ids below k data blocks in
+    ``objs``, the rest coding blocks in ``parity``) when replacing block b
+    alone makes it consistent, ``LOCATE_MANY`` (as uint32) otherwise.  Returns
+    ``lost`` (int32, ``nobj`` words, allocated when not given), which heal()
+    takes as it is.  vandrs w = 8 and isars with k <= 16, 2 <= m <= 4."""
+    k, m, w = params
+    nobj = objs.shape[0] if nobj is None else nobj
+    bs, _ = layout(coding, params, size)
+    _rows(objs, nobj, size, "objs")
+    _rows(parity, nobj, m * bs, "parity")
+    if lost is None:
+        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    _words(lost, nobj, "lost")
+    _lib.check(lib.leoec_locate_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                    nobj, parity.data_ptr(), _row_stride(parity), lost.data_ptr(),
+                                    _stream(stream)))
+    return lost
+
+
+def locate_rows(coding, params):
+    """leoec_locate_rows (no device needed): the ratios locate() tests the
+    syndromes with, ``m - 1`` lists of k GF(2^8) coefficients, list i - 1
+    holding C[i][j] / C[0][j] of the coding matrix C."""
+    k, m, w = params
+    cap = max((m - 1) * k, 1)
+    ratio = (ctypes.c_uint32 * cap)()
+    _lib.check(lib.leoec_locate_rows(_cid(coding), k, m, w, ratio, cap))
+    return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
+
+
 def repair(coding, params, blocks, block_size, repair_ids, out, nobj, stream=None):
     """leoec_repair_dev.  ``blocks``: list of k+m tensors-or-None, each
     ``[nobj, stride]`` with the block at byte 0 of every row (all the same
