@@ -2,28 +2,13 @@
 // No C++ exception crosses this boundary: anything thrown below becomes a
 // status code (the reference lets `new std::bad_alloc()` escape its catch
 // blocks and take the VM down, c_src/rscoding.cpp:69).
-#include <new>
-
 #include "../../include/leoec.h"
 #include "engine.hpp"
 #include "hostq.hpp"
 
 #define LEOEC_VERSION "0.1.0"
 
-namespace {
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return LEOEC_E_NOMEM;
-  } catch (...) {
-    return LEOEC_E_ARG;
-  }
-}
-
-}  // namespace
+using leoec::guarded;
 
 extern "C" {
 

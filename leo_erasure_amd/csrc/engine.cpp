@@ -41,12 +41,30 @@ uint64_t round_to(uint64_t n, uint64_t mult) {  // c_src/common.cpp:24-33
   return r ? n + mult - r : n;
 }
 
+}  // namespace
+
 uint64_t clamp_valid(uint64_t size, uint64_t start, uint64_t bs) {
   if (size <= start) return 0;
   return std::min<uint64_t>(size - start, bs);
 }
 
-}  // namespace
+Shard block_shard(int id, int k, uint64_t bs, uint64_t size, const uint8_t* objs,
+                  uint64_t obj_stride, const uint8_t* parity, uint64_t parity_stride) {
+  if (id < k)
+    return Shard{objs + (uint64_t)id * bs, obj_stride, clamp_valid(size, (uint64_t)id * bs, bs)};
+  return Shard{parity + (uint64_t)(id - k) * bs, parity_stride, bs};
+}
+
+int check_dev_batch(const uint8_t* objs, uint64_t obj_stride, uint64_t size, const uint8_t* parity,
+                    uint64_t parity_stride, int m, uint64_t bs) {
+  if (!objs || !parity) return LEOEC_E_ARG;
+  if (((uintptr_t)objs & 15u) || ((uintptr_t)parity & 15u) || (obj_stride & 15u) ||
+      (parity_stride & 15u))
+    return LEOEC_E_ARG;
+  if (bs >= (1ull << 32)) return LEOEC_E_BAD_SIZE;  // (then m * bs cannot overflow)
+  if (obj_stride < size || parity_stride < (uint64_t)m * bs) return LEOEC_E_ARG;
+  return LEOEC_OK;
+}
 
 // Coder::checkParams per class (rscoding.cpp:29-34, cauchycoding.cpp:30-35,
 // liberationcoding.cpp:29-36, irscoding.cpp:32-37) and the factory's
@@ -1404,11 +1422,11 @@ int op_encode_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   std::vector<Shard> in(k), par(m);
   std::vector<int> surv(k), want(m);
   for (int j = 0; j < k; ++j) {
-    in[j] = Shard{objs + (uint64_t)j * bs, obj_stride, clamp_valid(size, (uint64_t)j * bs, bs)};
+    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
     surv[j] = j;
   }
   for (int i = 0; i < m; ++i) {
-    par[i] = Shard{parity + (uint64_t)i * bs, parity_stride, bs};
+    par[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
     want[i] = k + i;
   }
   return apply(*c, surv.data(), in, want.data(), par, bs, nobj, s);
@@ -1439,16 +1457,10 @@ int op_decode_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_s
   const Code* c;
   if ((rc = get_code(coding, k, m, w, &c))) return rc;
   std::vector<Shard> in(k), out(want.size());
-  for (int i = 0; i < k; ++i) {
-    const int id = surv[i];
-    if (id < k)
-      in[i] = Shard{objs + (uint64_t)id * bs, obj_stride, clamp_valid(size, (uint64_t)id * bs, bs)};
-    else
-      in[i] = Shard{parity + (uint64_t)(id - k) * bs, parity_stride, bs};
-  }
+  for (int i = 0; i < k; ++i)
+    in[i] = block_shard(surv[i], k, bs, size, objs, obj_stride, parity, parity_stride);
   for (size_t o = 0; o < want.size(); ++o)
-    out[o] = Shard{objs + (uint64_t)want[o] * bs, obj_stride,
-                   clamp_valid(size, (uint64_t)want[o] * bs, bs)};
+    out[o] = block_shard(want[o], k, bs, size, objs, obj_stride, parity, parity_stride);
   return apply(*c, surv.data(), in, want.data(), out, bs, nobj, s);
 }
 

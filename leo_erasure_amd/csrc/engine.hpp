@@ -6,8 +6,10 @@
 
 #include <cstdint>
 #include <memory>
+#include <new>
 #include <vector>
 
+#include "../../include/leoec.h"
 #include "codes.hpp"
 #include "kernels.hpp"
 
@@ -83,6 +85,32 @@ class DeviceScope {
   int prev_ = -1;
   bool ok_ = true;
 };
+
+// No C++ exception crosses the C ABI: anything thrown below an entry point
+// becomes a status code.
+template <typename F>
+int guarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return LEOEC_E_NOMEM;
+  } catch (...) {
+    return LEOEC_E_ARG;
+  }
+}
+
+// Bytes of [start, start + bs) that lie inside an object of `size` bytes.
+uint64_t clamp_valid(uint64_t size, uint64_t start, uint64_t bs);
+// Block `id` of every object of a device batch: a data id (< k) lies in the
+// objs rows and is clipped to `size`, a coding id is whole, in the parity rows.
+Shard block_shard(int id, int k, uint64_t bs, uint64_t size, const uint8_t* objs,
+                  uint64_t obj_stride, const uint8_t* parity, uint64_t parity_stride);
+// The batch checks of the verify / heal / locate entry points, in this order:
+// null or not 16-byte aligned bases, strides not multiples of 16
+// (LEOEC_E_ARG); bs >= 2^32 (LEOEC_E_BAD_SIZE); a stride shorter than its row
+// (LEOEC_E_ARG).
+int check_dev_batch(const uint8_t* objs, uint64_t obj_stride, uint64_t size, const uint8_t* parity,
+                    uint64_t parity_stride, int m, uint64_t bs);
 
 // Operations behind the C ABI (argument checking included).
 int op_layout(int coding, int k, int m, int w, uint64_t size, uint64_t* bs, int* filled);

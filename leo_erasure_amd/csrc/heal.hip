@@ -17,7 +17,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <new>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -36,12 +35,6 @@ template <std::size_t... I>
 HealFn gf8_heal_pick(std::index_sequence<I...>, int k) {
   static HealFn (*const sel[])() = {&gf8_heal_launcher<(int)I + 1>...};
   return sel[k - 1]();
-}
-
-// The configurations gf8_heal serves: verify.hip's verify_fused (plans of
-// kind Plan::kGf at w = 8 within one launch's K x R).
-bool heal_fused_config(int coding, int k, int m, int w) {
-  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && w == 8 && k <= kMaxK && m <= kMaxR;
 }
 
 // The pattern tables on the devices: one per (coding, k, m, device), built
@@ -122,27 +115,17 @@ int heal_generic(const Code& c, uint8_t* objs, uint64_t obj_stride, uint64_t siz
     o0 = o1;
     if (mk == 0 || !recoverable(mk, k, m)) continue;
     heal_split(k, m, mk, surv.data(), want.data());
-    for (int i = 0; i < k; ++i) {
-      const int id = surv[i];
-      const uint64_t start = (uint64_t)(id < k ? id : id - k) * bs;
-      if (id < k)
-        in[i] = Shard{objs + first * obj_stride + start, obj_stride,
-                      size <= start ? 0 : (size - start < bs ? size - start : bs)};
-      else
-        in[i] = Shard{parity + first * parity_stride + start, parity_stride, bs};
-    }
+    const uint8_t* const ob = objs + first * obj_stride;
+    const uint8_t* const pb = parity + first * parity_stride;
+    for (int i = 0; i < k; ++i)
+      in[i] = block_shard(surv[i], k, bs, size, ob, obj_stride, pb, parity_stride);
     std::vector<int> ids;  // the lost ids with bytes to rebuild
     out.clear();
     for (int x = 0; x < __builtin_popcount(mk); ++x) {
       const int id = want[x];
-      const uint64_t start = (uint64_t)(id < k ? id : id - k) * bs;
-      if (id < k) {
-        if (start >= size) continue;  // wholly past `size`: nothing to write (as op_decode_dev)
-        out.push_back(Shard{objs + first * obj_stride + start, obj_stride,
-                            size - start < bs ? size - start : bs});
-      } else {
-        out.push_back(Shard{parity + first * parity_stride + start, parity_stride, bs});
-      }
+      // a data block wholly past `size`: nothing to write (as op_decode_dev)
+      if (id < k && (uint64_t)id * bs >= size) continue;
+      out.push_back(block_shard(id, k, bs, size, ob, obj_stride, pb, parity_stride));
       ids.push_back(id);
     }
     if (ids.empty()) continue;
@@ -162,26 +145,21 @@ int op_heal_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_str
   if (rc) return rc;
   if (k + m > kHealMaxIds) return LEOEC_E_UNSUPPORTED;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
-  if (!objs || !parity || !lost || !unhealed || lost == unhealed) return LEOEC_E_ARG;
+  if (!lost || !unhealed || lost == unhealed) return LEOEC_E_ARG;
   if (((uintptr_t)lost & 3u) || ((uintptr_t)unhealed & 3u)) return LEOEC_E_ARG;
-  if (((uintptr_t)objs & 15u) || ((uintptr_t)parity & 15u) || (obj_stride & 15u) ||
-      (parity_stride & 15u))
-    return LEOEC_E_ARG;
-  if (bs >= (1ull << 32)) return LEOEC_E_BAD_SIZE;
-  if (obj_stride < size || parity_stride < (uint64_t)m * bs) return LEOEC_E_ARG;
+  if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   if ((rc = device_init())) return rc;
   const Code* c;
   if ((rc = get_code(coding, k, m, w, &c))) return rc;
   const uint32_t* table = nullptr;
-  if (heal_fused_config(coding, k, m, w) && !(kMeasureBuild && knobs().heal_form == 1)) {
+  if (gf8_fused_config(coding, k, m, w) && !(kMeasureBuild && knobs().heal_form == 1)) {
     if ((rc = heal_table(*c, &table))) return rc;
   }
   if (!table)
     return heal_generic(*c, objs, obj_stride, size, bs, nobj, parity, parity_stride, lost, unhealed,
                         s);
   const HealFn fn = gf8_heal_pick(std::make_index_sequence<kMaxK>{}, k);
-  // as launch(GfApply): no grid above 2^31 - 1 workgroups at the narrowest tiles
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((bs + 1023) / 1024);
+  const uint64_t max_obj = gf8_max_objects(bs);
   for (uint64_t o0 = 0; o0 < nobj; o0 += max_obj) {
     HealArgs a;
     a.objs = objs + o0 * obj_stride;
@@ -219,7 +197,7 @@ int op_heal_rows(int coding, int k, int m, int w, uint32_t lost_mask, int* surv,
   for (int i = 0; i < bits; ++i) want[i] = wt[i];
   *nwant = bits;
   if (index)
-    *index = bits && heal_fused_config(coding, k, m, w) ? (int)heal_rank(k, m, lost_mask) : -1;
+    *index = bits && gf8_fused_config(coding, k, m, w) ? (int)heal_rank(k, m, lost_mask) : -1;
   if (coef && bits) {
     if (c->C.a.empty()) return LEOEC_E_UNSUPPORTED;  // liberation: no GF(2^w) matrix
     if (cap < bits * k) return LEOEC_E_ARG;
@@ -228,17 +206,6 @@ int op_heal_rows(int coding, int k, int m, int w, uint32_t lost_mask, int* surv,
     for (int i = 0; i < bits * k; ++i) coef[i] = rows[i];
   }
   return LEOEC_OK;
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return LEOEC_E_NOMEM;
-  } catch (...) {
-    return LEOEC_E_ARG;
-  }
 }
 
 }  // namespace

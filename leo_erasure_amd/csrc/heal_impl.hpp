@@ -10,6 +10,10 @@
 // from that record.  A clean object costs its workgroups one scalar load and
 // an exit; a damaged one reads its k survivors once and writes its lost
 // blocks once.
+//
+// Launch geometry and the workgroup -> (object, tile) decode are gf8_apply's
+// (gf8_grid_env, gf8_wg_tile in kernels_impl.hpp): HealArgs carries the same
+// tiles / nobj / tmap / tperm fields as Gf8Args.
 #pragma once
 
 #include "heal_table.hpp"
@@ -77,19 +81,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(W
 gf8_heal(const HealArgs a) {
   constexpr uint32_t CS = (uint32_t)kThreads * 16u;
   const uint32_t TBr = blockDim.x * 16u;  // tile width = workgroup size (256 or 64 lanes)
-  // workgroup -> (object, tile): gf8_apply's maps
-  const uint32_t b = a.tmap == 3   ? xcd_obj_map(blockIdx.x, gridDim.x, a.tiles)
-                     : a.tmap == 4 ? xcd_obj_map(blockIdx.x, gridDim.x, a.tperm)
-                                   : blockIdx.x;
   uint32_t obj, tile;
-  if (a.tmap == 1) {
-    tile = b / a.nobj;
-    obj = b - tile * a.nobj;
-  } else {
-    obj = b / a.tiles;
-    tile = b - obj * a.tiles;
-    if (a.tmap == 2) tile = (uint32_t)(((uint64_t)tile * a.tperm) % a.tiles);
-  }
+  gf8_wg_tile<0>(a, obj, tile);
   // 1. the object's mask: clean and unrecoverable objects leave here, the
   //    whole workgroup at once and before any barrier
   const uint32_t mask = __builtin_amdgcn_readfirstlane(a.lost[obj]);
@@ -182,32 +175,13 @@ gf8_heal(const HealArgs a) {
   }
 }
 
-// The grid of launch_gf8_check_t (tile width: 256 lanes, 64 above
-// kGf8NarrowBytes; the same tile maps) over the objects a describes.
+// The shipped gf8_apply form's grid (gf8_grid_env) over the objects a
+// describes; a.nobj is the caller's.
 template <int K>
 int launch_gf8_heal_t(HealArgs a, hipStream_t s) {
-  uint32_t wg = (uint32_t)kThreads;
-  const int force = gf8_wg_env();
-  if (force == 64 || (force == 0 && a.bs > kGf8NarrowBytes)) wg = 64;
-  const uint32_t tb = wg * 16u;
-  a.tiles = (uint32_t)(((uint64_t)a.bs + tb - 1) / tb);
-  a.tmap = (uint32_t)gf8_tile_map();
-  a.tperm = 1;
-  if (a.tmap == 0 && !gf8_tile_map_set()) {
-    if (a.tiles <= kObjMapMaxTiles) {
-      a.tmap = 3;
-    } else if (a.tiles >= kSegMapMinTiles) {
-      a.tmap = 4;
-      a.tperm = kSegMapGroup;
-    }
-  }
-  if (a.tmap == 4 && gf8_tile_group() > 0) a.tperm = (uint32_t)gf8_tile_group();
-  if (a.tmap == 2) {  // stride ~ tiles / 16, coprime with tiles
-    uint32_t q = a.tiles / 16u + 1u;
-    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-    while (gcd(q, a.tiles) != 1u) ++q;
-    a.tperm = q % a.tiles ? q % a.tiles : 1u;
-  }
+  const Gf8Grid g = gf8_grid_env(a.bs);
+  const uint32_t wg = g.wg;
+  gf8_set_grid(a, g, a.nobj);
   hipLaunchKernelGGL((gf8_heal<K, kMaxR, kGf8HealWaves>), dim3(a.nobj * a.tiles), dim3(wg), 0, s, a);
   return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
 }

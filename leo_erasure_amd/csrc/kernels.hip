@@ -250,6 +250,10 @@ bool gf8_tile_map_set() { return knobs().gf8_tmap_set; }
 int gf8_tile_group() { return knobs().gf8_tgroup; }
 }  // namespace detail
 
+bool gf8_fused_config(int coding, int k, int m, int w) {
+  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && w == 8 && k <= kMaxK && m <= kMaxR;
+}
+
 int launch(const GfApply& p, hipStream_t s) {
   if (p.K <= 0 || p.R <= 0 || (int)p.in.size() != p.K || (int)p.out.size() != p.R ||
       p.coef.size() != (size_t)p.K * p.R)
@@ -259,9 +263,7 @@ int launch(const GfApply& p, hipStream_t s) {
   if ((p.block_size & 15u) || p.block_size >= (1ull << 32)) return LEOEC_E_BAD_SIZE;
   if (!shards_ok(p.in) || !shards_ok(p.out)) return LEOEC_E_ARG;
   const uint32_t tiles = (uint32_t)((p.block_size + kTileBytes - 1) / kTileBytes);
-  // objects per launch bounded for the narrowest tiles (1 KiB, gf8_apply's
-  // 64-lane form) so no grid exceeds 2^31 - 1 workgroups
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((p.block_size + 1023) / 1024);
+  const uint64_t max_obj = gf8_max_objects(p.block_size);
   for (uint64_t o0 = 0; o0 < p.nobj; o0 += max_obj) {
     const uint64_t no = (p.nobj - o0 < max_obj) ? p.nobj - o0 : max_obj;
     for (int r0 = 0; r0 < p.R; r0 += kMaxR) {

@@ -75,6 +75,15 @@ struct LibDecApply {
 
 // Enqueue on `stream`; returns a leoec_status.
 int launch(const GfApply& plan, hipStream_t stream);
+// Objects per launch of a gf8 kernel: bounded for the narrowest tiles (1 KiB,
+// the 64-lane form) so that no grid exceeds 2^31 - 1 workgroups.
+inline uint64_t gf8_max_objects(uint64_t block_size) {
+  return (uint64_t)0x7FFFFFFF / ((block_size + 1023) / 1024);
+}
+// The configurations the fused gf8 kernels (gf8_check, gf8_heal, gf8_locate)
+// serve: the classes whose plans are Plan::kGf (a GF(2^w) coding matrix), at
+// w = 8, within one launch's K x R (kernels.hip).
+bool gf8_fused_config(int coding, int k, int m, int w);
 int launch(const BitApply& plan, hipStream_t stream);
 int launch(const GfBitApply& plan, hipStream_t stream);
 int launch(const LibDecApply& plan, hipStream_t stream);

@@ -461,33 +461,38 @@ __device__ __forceinline__ void gf8_store(const Gf8Args<K, R>& a, uint64_t o, ui
   }
 }
 
-// One workgroup per tile (PIPE = false), or a persistent grid that walks the
-// tiles and issues the loads of its next tile before computing the current
-// one (PIPE = true).
-// Workgroup-id remaps (xcd_group, xcd_obj_map): tile_maps.hpp, CPU-tested
-// for bijectivity (tests/test_tile_maps.py).
-//
-// Object-interleaved XCD map: with the dispatcher dealing workgroup ids
-// round-robin over the 8 XCDs, give XCD x the objects o = x (mod 8) with all
-// of an object's `tiles` tiles in order, so neighbouring tiles (which share
-// the partial cache lines of packets that start mid-line) meet in one L2 at
-// about the same time, while the 8 XCDs still work on neighbouring objects.
-// Ids past the last whole group of 8 objects keep their place.  Used when an
-// object has at most kObjMapMaxTiles tiles (1 MiB objects: +2-3 % on gf8,
-// +1-2 % on cauchyrs, +4-8 % on liberation); with many tiles per object
-// (objects of 4 MiB and up) it measured 2-4 % slower than dispatch order.
-constexpr uint32_t kObjMapMaxTiles = 64;
-// Blocks of at least kSegMapMinTiles tiles (32 MiB objects: 3,277 tiles of
-// 1 KiB; 64 MiB: 6,554) run gf8_apply under tile map 4 with groups of
-// kSegMapGroup tiles: XCD x takes every 8th run of 128 consecutive tiles
-// (128 KiB of each block), so each L2 streams whole 128 KiB stretches of the
-// 14 blocks instead of every 8th KiB.  RS(10,4,8), one process each
-// (profiles/r02_v13_ab_tmap4_*.log): 64 x 64 MiB 0.720 / 0.734 -> 0.743 /
-// 0.744 of HBM peak (encode / decode), 128 x 32 MiB 0.722 / 0.736 -> 0.743 /
-// 0.742; 16 MiB (1,639 tiles) unchanged and 4 MiB (410 tiles) 1 % slower, so
-// smaller blocks keep id order.
-constexpr uint32_t kSegMapMinTiles = 2048;
-constexpr uint32_t kSegMapGroup = 128;
+// Workgroup-id remaps (xcd_group, xcd_obj_map) and the launch geometry that
+// picks one (gf8_grid, with the measured thresholds): tile_maps.hpp, CPU-tested
+// (tests/test_tile_maps.py).
+
+// Workgroup -> (object, tile) of gf8_apply and gf8_heal under the launch's
+// tile map (A: Gf8Args or HealArgs; tmap / tperm from gf8_grid).  gf8_check
+// and gf8_locate keep the same text inline.
+// XMAP: gf8_apply's compiled-in maps (Gf8Opt::xmap).  The struct is taken by
+// reference and its fields read where they are used (passed by value they are
+// fetched in one wide scalar load up front and the whole kernel's register
+// numbering shifts), and obj / tile are assigned once, at the end (assigned
+// through the references in the branches, gf8_apply<4,2> and <5,2> number
+// their SGPRs differently): the kernels' code objects are pinned byte for
+// byte (Kernels).
+template <int XMAP, class A>
+__device__ __forceinline__ void gf8_wg_tile(const A& a, uint32_t& obj, uint32_t& tile) {
+  const uint32_t b = XMAP == 1 ? xcd_group(blockIdx.x, gridDim.x)
+                     : (XMAP == 2 || a.tmap == 3) ? xcd_obj_map(blockIdx.x, gridDim.x, a.tiles)
+                     : a.tmap == 4                ? xcd_obj_map(blockIdx.x, gridDim.x, a.tperm)
+                                                  : blockIdx.x;
+  uint32_t o, t;
+  if (a.tmap == 1) {
+    t = b / a.nobj;
+    o = b - t * a.nobj;
+  } else {
+    o = b / a.tiles;
+    t = b - o * a.tiles;
+    if (a.tmap == 2) t = (uint32_t)(((uint64_t)t * a.tperm) % a.tiles);
+  }
+  obj = o;
+  tile = t;
+}
 
 // One workgroup of WG threads per tile (PIPE = false), or a persistent grid
 // that walks the tiles and issues the loads of its next tile before
@@ -520,19 +525,8 @@ gf8_apply(const Gf8Args<K, R> a) {
     __syncthreads();
   }
   if (!PIPE) {
-    const uint32_t b = XMAP == 1 ? xcd_group(blockIdx.x, gridDim.x)
-                       : (XMAP == 2 || a.tmap == 3) ? xcd_obj_map(blockIdx.x, gridDim.x, a.tiles)
-                       : a.tmap == 4                ? xcd_obj_map(blockIdx.x, gridDim.x, a.tperm)
-                                                    : blockIdx.x;
     uint32_t obj, tile;
-    if (a.tmap == 1) {
-      tile = b / a.nobj;
-      obj = b - tile * a.nobj;
-    } else {
-      obj = b / a.tiles;
-      tile = b - obj * a.tiles;
-      if (a.tmap == 2) tile = (uint32_t)(((uint64_t)tile * a.tperm) % a.tiles);
-    }
+    gf8_wg_tile<XMAP>(a, obj, tile);
     const uint32_t t0 = tile * TBr;
     const uint32_t off = t0 + threadIdx.x * 16u;
     const bool full = t0 + TBr <= a.vmin;  // wave-uniform
@@ -1385,9 +1379,49 @@ int gf8_tile_map();       // gf8_apply workgroup -> tile order (kernels.hip)
 int gf8_wg_env();         // LEOEC_GF8_WG override of the tile width (kernels.hip)
 bool gf8_tile_map_set();  // LEOEC_GF8_TMAP given (then no automatic xcd_obj_map)
 int gf8_tile_group();     // tiles per XCD group of tile map 4 (kernels.hip)
-// Blocks larger than this run gf8_apply with 64-lane workgroups: 1 MiB objects
-// (bs 104,960) keep 256 lanes, 2 MiB (209,792) and up take 64.
-constexpr uint64_t kGf8NarrowBytes = 160 * 1024;
+
+// gf8_grid (tile_maps.hpp) under the process's knobs.
+inline Gf8Grid gf8_grid_env(uint64_t block_size, int cpt = 1, bool width_free = true,
+                            uint32_t wg_default = (uint32_t)kThreads) {
+  return gf8_grid(block_size, cpt, width_free, wg_default, gf8_wg_env(), gf8_tile_map(),
+                  gf8_tile_map_set(), gf8_tile_group());
+}
+
+// The shards, tables, 0/1 coefficient sets and vmin of a launch over rows
+// [r0, r0 + R) x columns [j0, j0 + K) of p, objects from o0.  Returns the
+// count of 0/1 coefficients.
+template <int K, int R>
+int gf8_fill(Gf8Args<K, R>& a, const GfApply& p, int r0, int j0, uint64_t o0) {
+  a.one = a.zero = 0;
+  uint32_t vmin = 0xFFFFFFFFu;
+  int n01 = 0;
+  for (int j = 0; j < K; ++j) {
+    a.in[j] = dev_shard(p.in[j0 + j], o0);
+    vmin = a.in[j].valid < vmin ? a.in[j].valid : vmin;
+  }
+  for (int r = 0; r < R; ++r) {
+    a.out[r] = dev_shard(p.out[r0 + r], o0);
+    vmin = a.out[r].valid < vmin ? a.out[r].valid : vmin;
+    for (int j = 0; j < K; ++j) {
+      const uint32_t cf = p.coef[(size_t)(r0 + r) * p.K + j0 + j] & 0xFFu;
+      gf8_tables(cf, a.tab[r][j]);
+      if (cf == 1) a.one |= 1ull << (r * K + j);
+      if (cf == 0) a.zero |= 1ull << (r * K + j);
+      n01 += cf <= 1;
+    }
+  }
+  a.vmin = vmin;
+  return n01;
+}
+
+// The grid's share of the arguments, over `no` objects.
+template <class A>
+void gf8_set_grid(A& a, const Gf8Grid& g, uint64_t no) {
+  a.tiles = g.tiles;
+  a.nobj = (uint32_t)no;
+  a.tmap = g.tmap;
+  a.tperm = g.tperm;
+}
 
 // BRANCHY = -1: pick per launch from the coefficients (scalar-branch form
 // when enough coefficients are 0/1, the paired all-table form otherwise).
@@ -1397,54 +1431,11 @@ template <int K, int R, bool ACC, int CPT = kGf8Default.cpt, bool NT = kGf8Defau
           int XMAP = kGf8Default.xmap, bool BUF = false, bool ONES = false, bool EARLY = false>
 int launch_gf8_t(const GfApply& p, const Chunk& c, hipStream_t s) {
   Gf8Args<K, R> a;
-  a.one = a.zero = 0;
-  uint32_t vmin = 0xFFFFFFFFu;
-  int n01 = 0;
-  for (int j = 0; j < K; ++j) {
-    a.in[j] = dev_shard(p.in[c.j0 + j], c.o0);
-    vmin = a.in[j].valid < vmin ? a.in[j].valid : vmin;
-  }
-  for (int r = 0; r < R; ++r) {
-    a.out[r] = dev_shard(p.out[c.r0 + r], c.o0);
-    vmin = a.out[r].valid < vmin ? a.out[r].valid : vmin;
-    for (int j = 0; j < K; ++j) {
-      const uint32_t cf = p.coef[(size_t)(c.r0 + r) * p.K + c.j0 + j] & 0xFFu;
-      gf8_tables(cf, a.tab[r][j]);
-      if (cf == 1) a.one |= 1ull << (r * K + j);
-      if (cf == 0) a.zero |= 1ull << (r * K + j);
-      n01 += cf <= 1;
-    }
-  }
-  // Workgroup (= tile) width: WG lanes, or 64 lanes (1 KiB tiles) for blocks
-  // above kGf8NarrowBytes, where they measured 2-8 % faster (block
-  // size sweep); LEOEC_GF8_WG=64|256 forces one (A/B, parity tests).
-  uint32_t wg = (uint32_t)WG;
-  if (CPT == 1 && !PIPE) {
-    const int force = gf8_wg_env();
-    if (force == 64 || (force == 0 && p.block_size > kGf8NarrowBytes)) wg = 64;
-  }
-  const uint32_t tb = wg * 16u * CPT;
-  a.tiles = (uint32_t)((p.block_size + tb - 1) / tb);
-  a.vmin = vmin;
+  const int n01 = gf8_fill(a, p, c.r0, c.j0, c.o0);
+  const Gf8Grid g = gf8_grid_env(p.block_size, CPT, CPT == 1 && !PIPE, (uint32_t)WG);
+  const uint32_t wg = g.wg;
+  gf8_set_grid(a, g, c.no);
   a.total_tiles = (uint32_t)(c.no * a.tiles);
-  a.nobj = (uint32_t)c.no;
-  a.tmap = (uint32_t)gf8_tile_map();
-  a.tperm = 1;
-  if (a.tmap == 0 && !gf8_tile_map_set()) {  // shipped choice (measure build: unless forced)
-    if (a.tiles <= kObjMapMaxTiles) {
-      a.tmap = 3;
-    } else if (a.tiles >= kSegMapMinTiles) {
-      a.tmap = 4;
-      a.tperm = kSegMapGroup;
-    }
-  }
-  if (a.tmap == 4 && gf8_tile_group() > 0) a.tperm = (uint32_t)gf8_tile_group();
-  if (a.tmap == 2) {  // stride ~ tiles / 16, coprime with tiles (a bijection on tiles)
-    uint32_t q = a.tiles / 16u + 1u;
-    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-    while (gcd(q, a.tiles) != 1u) ++q;
-    a.tperm = q % a.tiles ? q % a.tiles : 1u;
-  }
   // per-dword VALU: general coefficient 5.5 (branchy) vs 5 (paired); a 1 costs
   // 1 and a 0 nothing in the branchy form
   const int n = R * K;

@@ -14,7 +14,6 @@
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
-#include <new>
 #include <utility>
 #include <vector>
 
@@ -35,8 +34,7 @@ LocateFn gf8_locate_pick(std::index_sequence<I...>, int k, int r) {
 }
 
 bool locate_served(int coding, int k, int m, int w) {
-  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && w == 8 && k <= kMaxK && m >= 2 &&
-         m <= kMaxR;
+  return gf8_fused_config(coding, k, m, w) && m >= 2;
 }
 
 // One word per lane, in place.
@@ -77,12 +75,8 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   std::vector<uint32_t> ratio;
   if ((rc = locate_code(coding, k, m, w, &c, &ratio))) return rc;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
-  if (!objs || !parity || !lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
-  if (((uintptr_t)objs & 15u) || ((uintptr_t)parity & 15u) || (obj_stride & 15u) ||
-      (parity_stride & 15u))
-    return LEOEC_E_ARG;
-  if (bs >= (1ull << 32)) return LEOEC_E_BAD_SIZE;
-  if (obj_stride < size || parity_stride < (uint64_t)m * bs) return LEOEC_E_ARG;
+  if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   if ((rc = device_init())) return rc;
   GfApply a;
   a.w = w;
@@ -91,16 +85,14 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   a.coef = c->C.a;  // the encoding rows: data blocks 0..k-1 in, coding blocks out
   a.in.resize(k);
   a.out.resize(m);
-  for (int j = 0; j < k; ++j) {
-    const uint64_t start = (uint64_t)j * bs;
-    a.in[j] = Shard{objs + start, obj_stride, size <= start ? 0 : (size - start < bs ? size - start : bs)};
-  }
-  for (int i = 0; i < m; ++i) a.out[i] = Shard{parity + (uint64_t)i * bs, parity_stride, bs};
+  for (int j = 0; j < k; ++j)
+    a.in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
+  for (int i = 0; i < m; ++i)
+    a.out[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
   a.block_size = bs;
   a.nobj = nobj;
   const LocateFn fn = gf8_locate_pick(std::make_index_sequence<kMaxK>{}, k, m);
-  // as op_verify_dev: no grid above 2^31 - 1 workgroups at the narrowest tiles
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((bs + 1023) / 1024);
+  const uint64_t max_obj = gf8_max_objects(bs);
   for (uint64_t o0 = 0; o0 < nobj; o0 += max_obj) {
     const uint64_t no = nobj - o0 < max_obj ? nobj - o0 : max_obj;
     if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
@@ -111,17 +103,6 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
   }
   return LEOEC_OK;
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return LEOEC_E_NOMEM;
-  } catch (...) {
-    return LEOEC_E_ARG;
-  }
 }
 
 }  // namespace

@@ -13,6 +13,10 @@
 // and ANDs that candidate mask (bit j < K data, bit K + i coding) into the
 // object's word, which starts at all ones.  locate_finish (locate.hip) reads
 // the words afterwards.
+//
+// Arguments and launch geometry are gf8_check's, that is gf8_apply's
+// (gf8_fill, gf8_grid_env); the launcher adds only the ratio tables.  The
+// kernel repeats gf8_check's frame as text (Kernels).
 #pragma once
 
 #include "verify_impl.hpp"
@@ -41,7 +45,8 @@ gf8_locate(const Gf8Args<K, R> a, const Gf8Ratio<K, R> t, uint32_t* __restrict__
     lds.t[i][1] = u32x4{c[4], 0u, 0u, 0u};
   }
   __syncthreads();
-  // workgroup -> (object, tile): gf8_apply's maps
+  // workgroup -> (object, tile): gf8_apply's maps (gf8_wg_tile's text: through
+  // the helper this kernel's code objects change, DESIGN.md, Kernels)
   const uint32_t b = a.tmap == 3   ? xcd_obj_map(blockIdx.x, gridDim.x, a.tiles)
                      : a.tmap == 4 ? xcd_obj_map(blockIdx.x, gridDim.x, a.tperm)
                                    : blockIdx.x;
@@ -113,57 +118,21 @@ gf8_locate(const Gf8Args<K, R> a, const Gf8Ratio<K, R> t, uint32_t* __restrict__
   if (lane == 0u) atomicAnd(&lost[obj], mask);
 }
 
-// launch_gf8_check_t's arguments and grid (tile width: 256 lanes, 64 above
-// kGf8NarrowBytes; the same tile maps) over objects [o0, o0 + no) of p, plus
-// the ratio tables.  p.out holds the stored coding blocks; ratio: the
+// launch_gf8_check_t's arguments and grid over objects [o0, o0 + no) of p,
+// plus the ratio tables.  p.out holds the stored coding blocks; ratio: the
 // (R - 1) x K words of locate_build_rows for p.coef.
 template <int K, int R>
 int launch_gf8_locate_t(const GfApply& p, const uint32_t* ratio, uint64_t o0, uint64_t no,
                         uint32_t* lost, hipStream_t s) {
   Gf8Args<K, R> a;
   Gf8Ratio<K, R> t;
-  a.one = a.zero = 0;
-  uint32_t vmin = 0xFFFFFFFFu;
-  for (int j = 0; j < K; ++j) {
-    a.in[j] = dev_shard(p.in[j], o0);
-    vmin = a.in[j].valid < vmin ? a.in[j].valid : vmin;
-  }
-  for (int r = 0; r < R; ++r) {
-    a.out[r] = dev_shard(p.out[r], o0);
-    vmin = a.out[r].valid < vmin ? a.out[r].valid : vmin;
-    for (int j = 0; j < K; ++j) {
-      const uint32_t cf = p.coef[(size_t)r * K + j] & 0xFFu;
-      gf8_tables(cf, a.tab[r][j]);
-      if (cf == 1) a.one |= 1ull << (r * K + j);
-      if (cf == 0) a.zero |= 1ull << (r * K + j);
-      if (r > 0) gf8_tables(ratio[(size_t)(r - 1) * K + j] & 0xFFu, t.tab[r - 1][j]);
-    }
-  }
-  uint32_t wg = (uint32_t)kThreads;
-  const int force = gf8_wg_env();
-  if (force == 64 || (force == 0 && p.block_size > kGf8NarrowBytes)) wg = 64;
-  const uint32_t tb = wg * 16u;
-  a.tiles = (uint32_t)((p.block_size + tb - 1) / tb);
-  a.vmin = vmin;
+  gf8_fill(a, p, 0, 0, o0);
+  for (int r = 1; r < R; ++r)
+    for (int j = 0; j < K; ++j) gf8_tables(ratio[(size_t)(r - 1) * K + j] & 0xFFu, t.tab[r - 1][j]);
+  const Gf8Grid g = gf8_grid_env(p.block_size);
+  const uint32_t wg = g.wg;
+  gf8_set_grid(a, g, no);
   a.total_tiles = (uint32_t)(no * a.tiles);
-  a.nobj = (uint32_t)no;
-  a.tmap = (uint32_t)gf8_tile_map();
-  a.tperm = 1;
-  if (a.tmap == 0 && !gf8_tile_map_set()) {
-    if (a.tiles <= kObjMapMaxTiles) {
-      a.tmap = 3;
-    } else if (a.tiles >= kSegMapMinTiles) {
-      a.tmap = 4;
-      a.tperm = kSegMapGroup;
-    }
-  }
-  if (a.tmap == 4 && gf8_tile_group() > 0) a.tperm = (uint32_t)gf8_tile_group();
-  if (a.tmap == 2) {  // stride ~ tiles / 16, coprime with tiles
-    uint32_t q = a.tiles / 16u + 1u;
-    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-    while (gcd(q, a.tiles) != 1u) ++q;
-    a.tperm = q % a.tiles ? q % a.tiles : 1u;
-  }
   hipLaunchKernelGGL((gf8_locate<K, R, kGf8CheckWaves>), dim3(a.total_tiles), dim3(wg), 0, s, a, t,
                      lost + o0);
   return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;

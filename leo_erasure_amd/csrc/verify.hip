@@ -13,7 +13,6 @@
 // (tests/host_sanitize) links those against stand-in kernels and a stand-in
 // HIP header that know nothing of these launches.  For the same reason the
 // gf_init warm-up does not load this unit's kernels.
-#include <new>
 #include <utility>
 
 #include "engine.hpp"
@@ -36,12 +35,11 @@ CheckFn gf8_check_pick(std::index_sequence<I...>, int k, int r) {
   return sel[k - 1](r);
 }
 
-// The configurations gf8_check serves: the classes whose plans are
-// Plan::kGf (a GF(2^w) coding matrix), at w = 8, within one launch's K x R.
-// LEOEC_VERIFY_FORM=1 (measurement build): always two-pass.
+// gf8_check serves gf8_fused_config; LEOEC_VERIFY_FORM=1 (measurement build):
+// always two-pass.
 bool verify_fused(int coding, int k, int m, int w) {
   if (kMeasureBuild && knobs().verify_form == 1) return false;
-  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && w == 8 && k <= kMaxK && m <= kMaxR;
+  return gf8_fused_config(coding, k, m, w);
 }
 
 // Workspace row (obj, i) = the freshly encoded coding block i of the chunk's
@@ -87,13 +85,9 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
   if (rc) return rc;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
-  if (!objs || !parity || !flags || ((uintptr_t)flags & 3u)) return LEOEC_E_ARG;
-  if (((uintptr_t)objs & 15u) || ((uintptr_t)parity & 15u) || (obj_stride & 15u) ||
-      (parity_stride & 15u))
-    return LEOEC_E_ARG;
-  uint64_t per;  // workspace bytes of one object
-  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || bs >= (1ull << 32)) return LEOEC_E_BAD_SIZE;
-  if (obj_stride < size || parity_stride < per) return LEOEC_E_ARG;
+  if (!flags || ((uintptr_t)flags & 3u)) return LEOEC_E_ARG;
+  if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
+  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
   const bool fused = verify_fused(coding, k, m, w);
   if (!fused && (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per))
     return LEOEC_E_ARG;
@@ -103,12 +97,11 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   std::vector<Shard> in(k), par(m);
   std::vector<int> surv(k), want(m);
   for (int j = 0; j < k; ++j) {
-    const uint64_t start = (uint64_t)j * bs;
-    in[j] = Shard{objs + start, obj_stride, size <= start ? 0 : (size - start < bs ? size - start : bs)};
+    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
     surv[j] = j;
   }
   for (int i = 0; i < m; ++i) {
-    par[i] = Shard{parity + (uint64_t)i * bs, parity_stride, bs};
+    par[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
     want[i] = k + i;
   }
   std::shared_ptr<const Plan> plan;
@@ -126,8 +119,7 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     a.block_size = bs;
     a.nobj = nobj;
     const CheckFn fn = gf8_check_pick(std::make_index_sequence<kMaxK>{}, k, m);
-    // as launch(GfApply): no grid above 2^31 - 1 workgroups at the narrowest tiles
-    const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((bs + 1023) / 1024);
+    const uint64_t max_obj = gf8_max_objects(bs);
     for (uint64_t o0 = 0; o0 < nobj; o0 += max_obj) {
       const uint64_t no = nobj - o0 < max_obj ? nobj - o0 : max_obj;
       if ((rc = fn(a, o0, no, flags, s))) return rc;
@@ -153,17 +145,6 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
   }
   return LEOEC_OK;
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return LEOEC_E_NOMEM;
-  } catch (...) {
-    return LEOEC_E_ARG;
-  }
 }
 
 }  // namespace

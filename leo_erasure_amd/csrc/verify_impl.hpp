@@ -10,6 +10,11 @@
 // reduces it to one bit per coding block and ORs the bits of a wave into the
 // object's flag word, so a clean stripe writes nothing: the check reads the
 // k + m blocks once and that is all its traffic.
+//
+// Arguments and launch geometry are gf8_apply's own (gf8_fill, gf8_grid_env in
+// kernels_impl.hpp).  The kernel's frame (LDS staging, workgroup -> (object,
+// tile) decode, tile arithmetic) repeats gf8_apply's as text: moved into
+// shared device helpers it compiles to other bytes (Kernels).
 #pragma once
 
 #include "kernels_impl.hpp"
@@ -40,7 +45,8 @@ gf8_check(const Gf8Args<K, R> a, uint32_t* __restrict__ flags) {
     lds.t[i][1] = u32x4{t[4], 0u, 0u, 0u};
   }
   __syncthreads();
-  // workgroup -> (object, tile): gf8_apply's maps
+  // workgroup -> (object, tile): gf8_apply's maps (gf8_wg_tile's text: through
+  // the helper this kernel's code objects change, DESIGN.md, Kernels)
   const uint32_t b = a.tmap == 3   ? xcd_obj_map(blockIdx.x, gridDim.x, a.tiles)
                      : a.tmap == 4 ? xcd_obj_map(blockIdx.x, gridDim.x, a.tperm)
                                    : blockIdx.x;
@@ -70,55 +76,18 @@ gf8_check(const Gf8Args<K, R> a, uint32_t* __restrict__ flags) {
   if (mask != 0u && (threadIdx.x & 63u) == 0u) atomicOr(&flags[obj], mask);
 }
 
-// Fills Gf8Args as launch_gf8_t does for the shipped gf8_apply form (tile
-// width: 256 lanes, 64 above kGf8NarrowBytes; the same tile maps) and
-// launches gf8_check over objects [o0, o0 + no) of p.  p.out holds the stored
-// coding blocks; p.R = R <= kMaxR rows, p.K = K <= kMaxK inputs.
+// launch_gf8_t's arguments (gf8_fill) and the shipped gf8_apply form's grid
+// (gf8_grid_env) over objects [o0, o0 + no) of p, for gf8_check.  p.out holds
+// the stored coding blocks; p.R = R <= kMaxR rows, p.K = K <= kMaxK inputs.
 template <int K, int R>
 int launch_gf8_check_t(const GfApply& p, uint64_t o0, uint64_t no, uint32_t* flags,
                        hipStream_t s) {
   Gf8Args<K, R> a;
-  a.one = a.zero = 0;
-  uint32_t vmin = 0xFFFFFFFFu;
-  for (int j = 0; j < K; ++j) {
-    a.in[j] = dev_shard(p.in[j], o0);
-    vmin = a.in[j].valid < vmin ? a.in[j].valid : vmin;
-  }
-  for (int r = 0; r < R; ++r) {
-    a.out[r] = dev_shard(p.out[r], o0);
-    vmin = a.out[r].valid < vmin ? a.out[r].valid : vmin;
-    for (int j = 0; j < K; ++j) {
-      const uint32_t cf = p.coef[(size_t)r * K + j] & 0xFFu;
-      gf8_tables(cf, a.tab[r][j]);
-      if (cf == 1) a.one |= 1ull << (r * K + j);
-      if (cf == 0) a.zero |= 1ull << (r * K + j);
-    }
-  }
-  uint32_t wg = (uint32_t)kThreads;
-  const int force = gf8_wg_env();
-  if (force == 64 || (force == 0 && p.block_size > kGf8NarrowBytes)) wg = 64;
-  const uint32_t tb = wg * 16u;
-  a.tiles = (uint32_t)((p.block_size + tb - 1) / tb);
-  a.vmin = vmin;
+  gf8_fill(a, p, 0, 0, o0);
+  const Gf8Grid g = gf8_grid_env(p.block_size);
+  const uint32_t wg = g.wg;
+  gf8_set_grid(a, g, no);
   a.total_tiles = (uint32_t)(no * a.tiles);
-  a.nobj = (uint32_t)no;
-  a.tmap = (uint32_t)gf8_tile_map();
-  a.tperm = 1;
-  if (a.tmap == 0 && !gf8_tile_map_set()) {
-    if (a.tiles <= kObjMapMaxTiles) {
-      a.tmap = 3;
-    } else if (a.tiles >= kSegMapMinTiles) {
-      a.tmap = 4;
-      a.tperm = kSegMapGroup;
-    }
-  }
-  if (a.tmap == 4 && gf8_tile_group() > 0) a.tperm = (uint32_t)gf8_tile_group();
-  if (a.tmap == 2) {  // stride ~ tiles / 16, coprime with tiles
-    uint32_t q = a.tiles / 16u + 1u;
-    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-    while (gcd(q, a.tiles) != 1u) ++q;
-    a.tperm = q % a.tiles ? q % a.tiles : 1u;
-  }
 #ifdef LEOEC_MEASURE
   if constexpr (K == 10 && R == 4) {
     if (verify_form_env() == 2) {

@@ -49,13 +49,27 @@ def _rows(t, nobj, cols, what):
         raise ValueError(f"{what}: rows of {t.shape[1]} B, {cols} B needed")
 
 
-def encode(coding, params, objs, size, parity, nobj=None, stream=None):
-    """leoec_encode_dev: coding blocks of every object of the batch."""
+def _words(t, nobj, what):
+    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or (
+            t.numel() > 1 and t.stride(0) != 1):
+        raise ValueError(f"{what}: contiguous 1-D int32 device tensor expected")
+    if t.numel() < nobj:
+        raise ValueError(f"{what}: {t.numel()} words, {nobj} needed")
+
+
+def _batch(coding, params, objs, size, parity, nobj):
+    """(k, m, w, nobj, block size) of a batch whose tensors hold its rows."""
     k, m, w = params
     nobj = objs.shape[0] if nobj is None else nobj
     bs, _ = layout(coding, params, size)
     _rows(objs, nobj, size, "objs")
     _rows(parity, nobj, m * bs, "parity")
+    return k, m, w, nobj, bs
+
+
+def encode(coding, params, objs, size, parity, nobj=None, stream=None):
+    """leoec_encode_dev: coding blocks of every object of the batch."""
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
     _lib.check(lib.leoec_encode_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
                                     size, nobj, parity.data_ptr(), _row_stride(parity),
                                     _stream(stream)))
@@ -63,11 +77,7 @@ def encode(coding, params, objs, size, parity, nobj=None, stream=None):
 
 def decode(coding, params, objs, size, parity, erased, nobj=None, stream=None):
     """leoec_decode_dev: rebuild the erased data blocks in place in ``objs``."""
-    k, m, w = params
-    nobj = objs.shape[0] if nobj is None else nobj
-    bs, _ = layout(coding, params, size)
-    _rows(objs, nobj, size, "objs")
-    _rows(parity, nobj, m * bs, "parity")
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
     er = (ctypes.c_int * max(len(erased), 1))(*erased)
     _lib.check(lib.leoec_decode_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
                                     size, nobj, parity.data_ptr(), _row_stride(parity), er,
@@ -93,18 +103,10 @@ def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=
     ``workspace`` (uint8) are allocated when not given; a call on an explicit
     ``stream`` that needs a workspace must be given one, because the caching
     allocator orders a buffer's reuse only on the stream it knows about."""
-    k, m, w = params
-    nobj = objs.shape[0] if nobj is None else nobj
-    bs, _ = layout(coding, params, size)
-    _rows(objs, nobj, size, "objs")
-    _rows(parity, nobj, m * bs, "parity")
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
     if flags is None:
         flags = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    if flags.dtype != torch.int32 or not flags.is_cuda or flags.dim() != 1 or (
-            flags.numel() > 1 and flags.stride(0) != 1):
-        raise ValueError("flags: contiguous 1-D int32 device tensor expected")
-    if flags.numel() < nobj:
-        raise ValueError(f"flags: {flags.numel()} words, {nobj} needed")
+    _words(flags, nobj, "flags")
     need = verify_workspace(coding, params, size, nobj)
     if need and workspace is None:
         if stream is not None:
@@ -123,14 +125,6 @@ def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=
     return flags
 
 
-def _words(t, nobj, what):
-    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or (
-            t.numel() > 1 and t.stride(0) != 1):
-        raise ValueError(f"{what}: contiguous 1-D int32 device tensor expected")
-    if t.numel() < nobj:
-        raise ValueError(f"{what}: {t.numel()} words, {nobj} needed")
-
-
 def heal(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, stream=None):
     """leoec_heal_dev: rebuild in place the blocks every object has lost.
     Bit b of ``lost[o]`` (int32, ``nobj`` words) says block b of object o is
@@ -139,11 +133,7 @@ def heal(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, str
     not given): 0 for a healed or clean object, ``lost[o]`` for one that
     cannot be recovered (more than m bits, or a bit at or above k + m), of
     which nothing is written."""
-    k, m, w = params
-    nobj = objs.shape[0] if nobj is None else nobj
-    bs, _ = layout(coding, params, size)
-    _rows(objs, nobj, size, "objs")
-    _rows(parity, nobj, m * bs, "parity")
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
     if unhealed is None:
         unhealed = torch.empty(nobj, dtype=torch.int32, device=objs.device)
     _words(lost, nobj, "lost")
@@ -182,11 +172,7 @@ def locate(coding, params, objs, size, parity, nobj=None, lost=None, stream=None
     alone makes it consistent, ``LOCATE_MANY`` (as uint32) otherwise.  Returns
     ``lost`` (int32, ``nobj`` words, allocated when not given), which heal()
     takes as it is.  vandrs w = 8 and isars with k <= 16, 2 <= m <= 4."""
-    k, m, w = params
-    nobj = objs.shape[0] if nobj is None else nobj
-    bs, _ = layout(coding, params, size)
-    _rows(objs, nobj, size, "objs")
-    _rows(parity, nobj, m * bs, "parity")
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
     if lost is None:
         lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
     _words(lost, nobj, "lost")

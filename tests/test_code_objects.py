@@ -11,7 +11,20 @@ with the ROCm LLVM tools (clang-offload-bundler, llvm-readelf) and checks
 every kernel's metadata: at most kMaxScratch bytes of private segment per
 lane.  (Some gf8_apply instances for K >= 9 spill 2-30 VGPRs, up to 267 in
 the branchy variants no launch selects (kGf8Default.branchy = 0): 8-192
-bytes; the BASELINE kernels spill nothing: checked by name below.)"""
+bytes; the BASELINE kernels spill nothing: checked by name below.)
+
+The fused gf8 kernels (gf8_check, gf8_heal, gf8_locate) run under a 4-wave
+register budget and must spill nothing at any (K, R):
+ * gf8_check keeps gf8_apply's K input columns and the R stored coding
+   columns in VGPRs; under gf8_apply's 5-wave budget <10,4> spills 8 VGPRs
+   (verify_impl.hpp);
+ * gf8_heal (R = 4) keeps, unlike gf8_apply, the addresses and valid lengths
+   of its k + 4 blocks in SGPRs picked per object.  A form whose arithmetic
+   the compiler sinks into the per-row conditional stores spills 224 VGPRs at
+   K = 10 (heal_impl.hpp);
+ * gf8_locate is gf8_check up to the syndromes plus a cold branch that
+   multiplies one syndrome by up to 3 K ratios.  That branch must cost the
+   clean path nothing it can be measured by here."""
 import glob
 import os
 import re
@@ -90,3 +103,33 @@ def test_product_kernels_scratch(tmp_path):
     # the BASELINE configs' kernels: found, and no spill at all
     assert set(hot) == set(HOT), set(HOT) - set(hot)
     assert all(v == (0, 0) for v in hot.values()), hot
+
+
+# family -> (object stem, mangled-name prefix for (K, R) under the 4-wave budget, the Rs)
+FUSED = {
+    "check": ("gf8_check_k%d.o", "_ZN5leoec6detail9gf8_checkILi%dELi%dELi4EEE", (1, 2, 3, 4)),
+    "heal": ("gf8_heal_k%d.o", "_ZN5leoec6detail8gf8_healILi%dELi%dELi4EEE", (4,)),
+    "locate": ("gf8_locate_k%d.o", "_ZN5leoec6detail10gf8_locateILi%dELi%dELi4EEE", (2, 3, 4)),
+}
+
+
+@pytest.mark.skipif(not glob.glob(os.path.join(BUILD, "*.o")), reason="product objects not built")
+@pytest.mark.skipif(not (_tool("clang-offload-bundler") and _tool("llvm-readelf") and _tool("llvm-objcopy")),
+                    reason="ROCm LLVM tools absent")
+@pytest.mark.parametrize("family", sorted(FUSED))
+def test_fused_kernels_do_not_spill(tmp_path, family):
+    stem, frag, rs = FUSED[family]
+    found = {}
+    for K in range(1, 17):
+        obj = os.path.join(BUILD, stem % K)
+        assert os.path.exists(obj), obj
+        for name, md in kernel_notes(obj, str(tmp_path)):
+            for R in rs:
+                if name.startswith(frag % (K, R)):
+                    found[K, R] = (int(md["vgpr_spill_count"]),
+                                   int(md.get("private_segment_fixed_size", "0")),
+                                   int(md["vgpr_count"]))
+    assert sorted(found) == [(K, R) for K in range(1, 17) for R in rs], sorted(found)
+    assert all(v[:2] == (0, 0) for v in found.values()), found
+    # the 4-wave budget: at most 128 VGPRs
+    assert max(v[2] for v in found.values()) <= 128, found

@@ -374,6 +374,94 @@ def test_gf8_segment_map_forms(gpu, le, oracle, measure, tgroup):
         assert outs[1][o, :m * bs].tobytes() == b"".join(r[k:]), f"object {o}"
 
 
+_scrub_ref = {}
+
+
+def _scrub_case(le, oracle):
+    """vandrs(10,4,8), 13 objects (not a multiple of 8) of 200,000 bytes: 5
+    tiles per block at 256 lanes, 20 at 64, the last one ragged.  One byte of
+    every second object is damaged, alternately in a data block (in the
+    block's last tile at either width) and in a coding block.  Returns the
+    case, the damage list and what verify and locate must answer, from the
+    oracle (verify_helpers.data_damage_mask, locate_helpers.model_words);
+    computed once."""
+    import gpu_helpers as H
+    import locate_helpers as L
+    import verify_helpers as V
+    if not _scrub_ref:
+        case = H.edge_case(le, oracle, ("vandrs", 10, 4, 8), 200000, n=13)
+        k, m, bs = case.k, case.m, case.bs
+        last = (bs - 1) // 1024 * 1024  # first byte of the last 1 KiB tile (inside the last 4 KiB tile)
+        assert -(-bs // 4096) == 5 and -(-bs // 1024) == 20 and bs % 1024 != 0
+        dmg, flags = [], [0] * case.n
+        for i, o in enumerate(range(1, case.n, 2)):
+            if i % 2 == 0:
+                j = 3 * i % (k - 1)  # a whole data block: 0, 6, 3
+                pos = j * bs + last + 7
+                dmg.append(("objs", o, pos, V.BIT))
+                flags[o] = V.data_damage_mask(oracle, case, o, pos)
+                assert flags[o] == (1 << m) - 1
+            else:
+                c = i % m  # coding blocks 1, 3, 1
+                dmg.append(("parity", o, c * bs + last + 5, V.BIT))
+                flags[o] = 1 << c
+        words = L.model_words(oracle, le, case, dmg)
+        assert [w != 0 for w in words] == [o % 2 == 1 for o in range(case.n)], words
+        _scrub_ref["ref"] = (case, dmg, flags, words)
+    return _scrub_ref["ref"]
+
+
+def _scrub(gpu, le, case, dmg):
+    """verify, locate and heal (of what locate named) over the damaged batch:
+    (flags, words, the two arenas after heal)."""
+    import locate_helpers as L
+    n, g = case.n, case.guard
+    work, par = L.damaged_arenas(gpu, case, dmg)
+    objs, parity = work[g:g + n], par[1:1 + n]
+    flags = le.device.verify(case.cls, case.params, objs, case.size, parity)
+    lost = le.device.locate(case.cls, case.params, objs, case.size, parity)
+    unhealed = le.device.heal(case.cls, case.params, objs, case.size, parity, lost)
+    gpu.cuda.synchronize()
+    assert unhealed.tolist() == [0] * n
+    u32 = lambda t: [int(x) & 0xFFFFFFFF for x in t.tolist()]  # noqa: E731
+    return u32(flags), u32(lost), work, par
+
+
+@pytest.mark.parametrize("tmap", ["0", "1", "2", "3", "4"])
+def test_scrub_kernels_under_every_tile_map(gpu, le, oracle, measure, tmap):
+    """gf8_check, gf8_locate and gf8_heal take their workgroup -> (object,
+    tile) map from the launch geometry they share with gf8_apply: under every
+    forced tile map (map 4 with runs of 5 tiles), at both tile widths, verify
+    flags, locate words and the arenas after heal equal the tile-map-0 result,
+    and that equals the oracle's answer and the pristine batch; the edge
+    harness's own damaged batches verify as verify_helpers.expected_flags
+    says."""
+    import gpu_helpers as H
+    import verify_helpers as V
+    case, dmg, want_flags, want_words = _scrub_case(le, oracle)
+    snap, par_snap = case.dev(gpu)
+    for wg in (None, "64"):
+        if wg:
+            measure.setenv("LEOEC_GF8_WG", wg)
+        measure.delenv("LEOEC_GF8_TGROUP")
+        measure.setenv("LEOEC_GF8_TMAP", "0")
+        base = _scrub(gpu, le, case, dmg)
+        assert base[0] == want_flags, (wg, base[0])
+        assert base[1] == want_words, (wg, [hex(x) for x in base[1]])
+        assert not H.arena_diff(gpu, base[2], snap, case.guard, "heal, tile map 0: objs")
+        assert not H.arena_diff(gpu, base[3], par_snap, 1, "heal, tile map 0: parity")
+        measure.setenv("LEOEC_GF8_TMAP", tmap)
+        if tmap == "4":
+            measure.setenv("LEOEC_GF8_TGROUP", "5")
+        got = _scrub(gpu, le, case, dmg)
+        assert got[0] == base[0], (wg, tmap, got[0])
+        assert got[1] == base[1], (wg, tmap, [hex(x) for x in got[1]])
+        assert not H.arena_diff(gpu, got[2], base[2], case.guard, f"heal, tile map {tmap}: objs")
+        assert not H.arena_diff(gpu, got[3], base[3], 1, f"heal, tile map {tmap}: parity")
+        errors = V.check_case(gpu, le, oracle, case)
+        assert not errors, "\n".join(errors)
+
+
 @pytest.mark.parametrize("w", [16, 32])
 @pytest.mark.parametrize("env", [
     {},                                        # shipped: bitsliced planes (gfs_apply)

@@ -3,8 +3,10 @@ tile_maps.hpp), compiled for the CPU: every map the launchers use is a
 permutation of [0, n) — no tile skipped or done twice — including batches
 that are not whole rounds of 8 groups, and each XCD's share is what the map
 promises (whole objects for tile map 3, runs of consecutive tiles for tile
-map 4)."""
+map 4); and the launch geometry of the gf8 kernels (gf8_grid) at the
+boundaries of its rules."""
 import ctypes
+import math
 import os
 import subprocess
 
@@ -22,6 +24,10 @@ def maps(tmp_path_factory):
     L = ctypes.CDLL(so)
     L.tile_map_image.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     L.packet_lane_check.argtypes = [ctypes.c_uint32] * 6
+    L.gf8_grid_image.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_void_p]
+    L.gf8_grid_image.restype = None
     return L
 
 
@@ -98,3 +104,67 @@ def test_packet_lane_geometry(maps, wg, lb):
                     continue
                 rc = maps.packet_lane_check(bs, w, wg, lb, vin, vout)
                 assert rc == 0, (size, k, w, bs, vin, vout, rc)
+
+
+def grid(maps, bs, cpt=1, width_free=True, wg_default=256, force_wg=0, tmap=0, tmap_set=False,
+         tgroup=0):
+    out = np.zeros(4, dtype=np.uint32)
+    maps.gf8_grid_image(bs, cpt, int(width_free), wg_default, force_wg, tmap, int(tmap_set), tgroup,
+                        out.ctypes.data)
+    return tuple(int(x) for x in out)
+
+
+KiB = 1024
+# (arguments, (lanes, tiles per block, tile map, tperm)): the expected values
+# written out from the launchers' rules (256 lanes = 4 KiB tiles, 64 lanes =
+# 1 KiB tiles above 160 KiB; tile map 3 up to 64 tiles, 4 with groups of 128
+# from 2,048 tiles, dispatch order between)
+GRID_CASES = [
+    # the width switch
+    (dict(bs=160 * KiB), (256, 40, 3, 1)),
+    (dict(bs=160 * KiB + 16), (64, 161, 0, 1)),
+    # 64 / 65 tiles: tile map 3 or none (a forced width reaches the boundary)
+    (dict(bs=64 * 4 * KiB, force_wg=256), (256, 64, 3, 1)),
+    (dict(bs=64 * 4 * KiB + 16, force_wg=256), (256, 65, 0, 1)),
+    (dict(bs=64 * KiB, force_wg=64), (64, 64, 3, 1)),
+    (dict(bs=64 * KiB + 16, force_wg=64), (64, 65, 0, 1)),
+    # 2,047 / 2,048 tiles of 1 KiB: tile map 4 with groups of 128
+    (dict(bs=2047 * KiB), (64, 2047, 0, 1)),
+    (dict(bs=2047 * KiB + 16), (64, 2048, 4, 128)),
+    (dict(bs=2048 * KiB), (64, 2048, 4, 128)),
+    # a forced width on either side of the switch
+    (dict(bs=20000, force_wg=64), (64, 20, 3, 1)),
+    (dict(bs=1 << 20, force_wg=256), (256, 256, 0, 1)),
+    # the group of tile map 4: shipped, overridden, and under a forced map
+    (dict(bs=2048 * KiB, tgroup=5), (64, 2048, 4, 5)),
+    (dict(bs=20000, force_wg=64, tmap=4, tmap_set=True, tgroup=5), (64, 20, 4, 5)),
+    (dict(bs=20000, tmap=4, tmap_set=True), (256, 5, 4, 1)),
+    (dict(bs=20000, tmap=3, tmap_set=True, tgroup=5), (256, 5, 3, 1)),
+    # a forced map is kept, map 0 included (then no automatic choice)
+    (dict(bs=20000, tmap=0, tmap_set=True), (256, 5, 0, 1)),
+    (dict(bs=2048 * KiB, tmap=0, tmap_set=True), (64, 2048, 0, 1)),
+    (dict(bs=20000, tmap=1, tmap_set=True), (256, 5, 1, 1)),
+    (dict(bs=20000, tmap=1), (256, 5, 1, 1)),
+    # tile map 2: the first stride from tiles / 16 + 1 up that is coprime with tiles
+    (dict(bs=16 * 4 * KiB, tmap=2, tmap_set=True), (256, 16, 2, 3)),      # 2 -> 3
+    (dict(bs=104960, tmap=2, tmap_set=True), (256, 26, 2, 3)),            # 2 -> 3
+    (dict(bs=308 * KiB, tmap=2, tmap_set=True), (64, 308, 2, 23)),        # 20, 21, 22 -> 23
+    (dict(bs=16, tmap=2, tmap_set=True), (256, 1, 2, 1)),                 # 1 % 1 = 0 -> 1
+    # two columns per lane: 8 KiB tiles, and the width never changes
+    (dict(bs=209792, cpt=2, width_free=False), (256, 26, 3, 1)),
+    (dict(bs=209792, cpt=2, width_free=False, force_wg=64), (256, 26, 3, 1)),
+    (dict(bs=209792, cpt=1, width_free=False), (256, 52, 3, 1)),
+    # another compiled-in width (measurement forms)
+    (dict(bs=20000, wg_default=128), (128, 10, 3, 1)),
+]
+
+
+@pytest.mark.parametrize("args,want", GRID_CASES, ids=[str(i) for i in range(len(GRID_CASES))])
+def test_gf8_grid(maps, args, want):
+    got = grid(maps, **args)
+    assert got == want, (args, got)
+    wg, tiles, tmap, tperm = got
+    cpt = args.get("cpt", 1)
+    assert (tiles - 1) * wg * 16 * cpt < args["bs"] <= tiles * wg * 16 * cpt
+    if tmap == 2:
+        assert 1 <= tperm and math.gcd(tperm, tiles) == 1

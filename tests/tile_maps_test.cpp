@@ -23,6 +23,17 @@ int tile_map_image(int map, uint32_t n, uint32_t tiles, uint32_t* out) {
   return 0;
 }
 
+// gf8_grid's {wg, tiles, tmap, tperm} into out.
+void gf8_grid_image(uint64_t block_size, int cpt, int width_free, uint32_t wg_default, int force_wg,
+                    int tmap_knob, int tmap_set, int tgroup, uint32_t* out) {
+  const leoec::detail::Gf8Grid g = leoec::detail::gf8_grid(
+      block_size, cpt, width_free != 0, wg_default, force_wg, tmap_knob, tmap_set != 0, tgroup);
+  out[0] = g.wg;
+  out[1] = g.tiles;
+  out[2] = g.tmap;
+  out[3] = g.tperm;
+}
+
 // The packet kernels' lane geometry (tile_maps.hpp packet_*) over one
 // object of block size bs = w packets, WG-lane workgroups of LB bytes per
 // lane, input blocks holding valid_in data bytes and output blocks valid_out.
