@@ -242,7 +242,65 @@ int leoec_locate_dev(int coding, int k, int m, int w, const uint8_t *objs, uint6
                      uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
                      uint32_t *lost, void *stream);
 
+/* Workspace bytes leoec_locate_ws_dev wants for this batch: 0 for everything
+ * leoec_locate_dev serves, nobj * m * block_size (one pass) for cauchyrs and
+ * liberation; LEOEC_E_BAD_SIZE when that overflows; bytes == NULL:
+ * LEOEC_E_ARG.  Configurations leoec_locate_ws_dev does not serve, and invalid
+ * ones, get its statuses.  Needs no device. */
+int leoec_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                  uint64_t *bytes);
+
+/* leoec_locate_dev with a workspace, which adds the bitmatrix classes.  Words,
+ * layout, alignment, stride rules and the reading of bytes past `size` are
+ * leoec_locate_dev's: every word of lost is overwritten with 0, one bit
+ * b < k + m or LEOEC_LOCATE_MANY, and the words go into leoec_heal_dev as they
+ * are; objs and parity are never written.  The workspace's contents after the
+ * call are unspecified.
+ * Served:
+ *   (a) everything leoec_locate_dev serves: the call is forwarded to it, the
+ *       query returns 0 and workspace may be NULL;
+ *   (b) cauchyrs and liberation with m >= 2, k + m <= 32 and
+ *       (m-1) * k * w <= 768 (the ratio table travels as a kernel argument).
+ * Everything else (vandrs w = 16 / 32, w = 8 with k > 16 or m > 4, bitmatrix
+ * m = 1, k + m > 32, a larger table such as cauchyrs(10,4,32)) is
+ * LEOEC_E_UNSUPPORTED, returned before the device is opened; invalid
+ * parameters keep their leoec_check_params status; nobj == 0 is LEOEC_OK.
+ * workspace for (b): device, 16-byte aligned, at least m * block_size bytes
+ * (one object), else LEOEC_E_ARG; a smaller workspace than the query's gives
+ * the same words in more chunks of objects on the same stream.
+ * How (b) tells: a block is w packets.  Per bit position of a packet, the w
+ * bits the packets of syndrome s_i = stored coding block i ^ encoding of the
+ * data hold there are all zero (clean), non-zero in one i only (coding block
+ * i), or s_i = B[i][j] B[0][j]^-1 s_0 over GF(2) for every i (data block j),
+ * B[i][j] being the w x w blocks of the coding bitmatrix; an object's answer
+ * is the block that fits every position.  That is unique because every
+ * B[i][j] and every 2w x 2w minor of two coding rows and two data columns is
+ * invertible, which every call checks (leoec_locate_bitrows).
+ * The limit at m = 2 is leoec_locate_dev's and holds for every liberation
+ * call: two damaged blocks may be reported as a third.  At k + m = 32 the bit
+ * of the last coding block (id 31) is LEOEC_LOCATE_MANY's own: that word says
+ * either, and leoec_heal_dev reads it as block 31.
+ * For (b) the call allocates nothing, uploads nothing and never synchronises:
+ * per chunk the class's encode into the workspace, a memset and two launches
+ * on `stream`.  The first call on a device loads its own code object (1-2 ms);
+ * the leoec_gf_init warm-up does not cover it. */
+int leoec_locate_ws_dev(int coding, int k, int m, int w, const uint8_t *objs, uint64_t obj_stride,
+                        uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
+                        uint32_t *lost, void *workspace, uint64_t workspace_bytes, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
+
+/* The GF(2) ratios leoec_locate_ws_dev tests the syndromes of cauchyrs and
+ * liberation with; needs no device.  rows (cap >= (m-1) * k * w words): word
+ * ((i-1) * k + j) * w + r is row r of T[i][j] = B[i][j] B[0][j]^-1, i = 1..m-1;
+ * bit c (bit 0 = packet 0) is set iff syndrome packet c of coding block 0
+ * feeds the prediction of packet r of coding block i.  rows == NULL or cap too
+ * small: LEOEC_E_ARG.  Serves class (b) of leoec_locate_ws_dev only and gives
+ * its statuses otherwise; vandrs and isars are LEOEC_E_UNSUPPORTED (their
+ * table is leoec_locate_rows).  While building T the two properties the
+ * answer's uniqueness rests on are checked (every block and every 2w x 2w
+ * minor invertible): LEOEC_E_UNSUPPORTED if either fails. */
+int leoec_locate_bitrows(int coding, int k, int m, int w, uint32_t *rows, int cap);
 
 /* The ratios leoec_locate_dev tests the syndromes with; needs no device.
  * ratio (cap >= (m-1) * k words): row i-1 holds T[i][0..k) = C[i][j] / C[0][j]

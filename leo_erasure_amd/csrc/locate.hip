@@ -11,6 +11,15 @@
 //                   wave ANDs its candidate mask into its object's word;
 //   locate_finish   all ones -> 0, exactly one bit -> kept, anything else ->
 //                   LEOEC_LOCATE_MANY.
+// leoec_locate_ws_dev adds the bitmatrix classes (cauchyrs, liberation), which
+// have no fused check: per chunk of objects that the caller's workspace holds,
+//   encode plan     the class's ordinary encode into the workspace (as
+//                   verify.hip's two-pass path);
+//   memset          the chunk's words to all ones;
+//   bit_locate      below: syndromes = workspace ^ stored coding blocks, the
+//                   packet form of the test (locate_bitrows.hpp);
+//   locate_finish.
+// Everything leoec_locate_dev serves is forwarded to it.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
@@ -18,6 +27,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "locate_bitrows.hpp"
 #include "locate_impl.hpp"
 #include "locate_rows.hpp"
 
@@ -105,10 +115,234 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   return LEOEC_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The bitmatrix classes: leoec_locate_ws_dev.
+
+constexpr int kBitLocLanes = 64;                       // one wave per workgroup
+constexpr uint32_t kBitLocTile = kBitLocLanes * 16u;   // bytes of every packet per workgroup
+constexpr int kBitLocWords = 768;                      // (m - 1) k w at most: 3 KiB of argument
+
+// ws: the chunk's freshly encoded coding blocks, object o at o * per
+// (per = m bs, packed: row q = i w + r at q * ps is packet r of coding block
+// i); parity: the stored ones, object o at o * parity_stride, the same rows.
+struct BitLocArgs {
+  const uint8_t* ws;
+  const uint8_t* parity;
+  uint64_t parity_stride;
+  uint64_t per;
+  uint32_t ps, tiles, k, m, w;
+  uint32_t rows[kBitLocWords];  // locate_build_bitrows' words
+};
+static_assert(sizeof(BitLocArgs) + sizeof(uint32_t*) <= 3200, "kernel argument segment");
+
+// One workgroup (one wave) per (object, 1 KiB of packet offsets), one 16-byte
+// column per lane, w a runtime value.  Lanes past the packet read the tile's
+// first column and count as zero syndromes, which fit every block.
+// Clean path: the m w syndrome rows ORed per coding block, one ballot per
+// block; a wave with no non-zero syndrome ends there and writes nothing.
+// Dirty path: coding block i is a candidate when no syndrome but s_i is
+// non-zero; data blocks only when every syndrome is (every B[i][j] is
+// invertible: a column that fits a data block is non-zero in every syndrome
+// or in none).  Then the w packets of s_0 go to LDS (each lane reads back only
+// what it wrote: no barrier), every s_i[r] is loaded once and compared with
+// the XOR of the s_0 packets its row word names, for every data block still
+// in the running (row words by scalar loads from the argument).  lost[o]: the
+// word of object o of this launch (all ones beforehand).
+__global__ void __launch_bounds__(kBitLocLanes)
+bit_locate(const BitLocArgs a, uint32_t* __restrict__ lost) {
+  extern __shared__ u32x4 bit_locate_s0[];  // [w][kBitLocLanes]
+  const uint32_t obj = blockIdx.x / a.tiles;
+  const uint32_t tile = blockIdx.x - obj * a.tiles;
+  const uint32_t t0 = tile * kBitLocTile;  // < ps
+  const uint32_t off = t0 + threadIdx.x * 16u;
+  const bool in = off < a.ps;  // ps is a multiple of 16: the column lies inside the packet
+  const uint32_t o = in ? off : t0;
+  const uint8_t* const x = a.ws + (uint64_t)obj * a.per + o;
+  const uint8_t* const y = a.parity + (uint64_t)obj * a.parity_stride + o;
+  const uint32_t rows = a.m * a.w;
+  uint32_t dirty = 0;  // wave-uniform: bit i set when any lane's syndrome of block i is non-zero
+  for (uint32_t i = 0, q = 0; i < a.m; ++i) {
+    uint32_t nz = 0;
+#pragma unroll 4
+    for (uint32_t r = 0; r < a.w; ++r, ++q) {
+      const u32x4 e = ld16<false>(x + (uint64_t)q * a.ps);
+      const u32x4 p = ld16<true>(y + (uint64_t)q * a.ps);
+      nz |= (e[0] ^ p[0]) | (e[1] ^ p[1]) | (e[2] ^ p[2]) | (e[3] ^ p[3]);
+    }
+    if (__builtin_amdgcn_ballot_w64(in && nz != 0u) != 0ull) dirty |= 1u << i;
+  }
+  if (dirty == 0u) return;
+  // The cold branch.
+  auto syndrome = [&](uint32_t q) {
+    const u32x4 e = ld16<false>(x + (uint64_t)q * a.ps);
+    const u32x4 p = ld16<true>(y + (uint64_t)q * a.ps);
+    const uint32_t keep = in ? ~0u : 0u;
+    return u32x4{(e[0] ^ p[0]) & keep, (e[1] ^ p[1]) & keep, (e[2] ^ p[2]) & keep,
+                 (e[3] ^ p[3]) & keep};
+  };
+  uint32_t mask = 0;
+  for (uint32_t i = 0; i < a.m; ++i)
+    if ((dirty & ~(1u << i)) == 0u) mask |= 1u << (a.k + i);
+  if (dirty == (1u << a.m) - 1u) {  // m <= 31
+    u32x4* const s0 = bit_locate_s0 + threadIdx.x;
+    for (uint32_t c = 0; c < a.w; ++c) s0[c * kBitLocLanes] = syndrome(c);
+    const uint32_t all = (1u << a.k) - 1u;  // k <= 30
+    uint32_t notfit = 0;                    // wave-uniform: data blocks some column does not fit
+    for (uint32_t q = a.w; q < rows && notfit != all; ++q) {
+      const uint32_t i = q / a.w, r = q - i * a.w;
+      const u32x4 s = syndrome(q);
+      for (uint32_t j = 0; j < a.k; ++j) {
+        if ((notfit >> j) & 1u) continue;
+        u32x4 p = s;
+        for (uint32_t t = a.rows[((i - 1u) * a.k + j) * a.w + r]; t != 0u; t &= t - 1u) {
+          const u32x4 v = s0[(uint32_t)__builtin_ctz(t) * kBitLocLanes];
+          p[0] ^= v[0];
+          p[1] ^= v[1];
+          p[2] ^= v[2];
+          p[3] ^= v[3];
+        }
+        if (__builtin_amdgcn_ballot_w64((p[0] | p[1] | p[2] | p[3]) != 0u) != 0ull) notfit |= 1u << j;
+      }
+    }
+    mask |= ~notfit & all;
+  }
+  if (threadIdx.x == 0u) atomicAnd(&lost[obj], mask);
+}
+
+bool bit_class(int coding) { return coding == LEOEC_CAUCHYRS || coding == LEOEC_LIBERATION; }
+
+bool bit_locate_served(int coding, int k, int m, int w) {
+  return bit_class(coding) && m >= 2 && k + m <= 32 && (m - 1) * k * w <= kBitLocWords;
+}
+
+// The code and its row words; needs no device.
+int bit_locate_code(int coding, int k, int m, int w, const Code** c, std::vector<uint32_t>* rows) {
+  int rc = check_params(coding, k, m, w);
+  if (rc) return rc;
+  if (!bit_locate_served(coding, k, m, w)) return LEOEC_E_UNSUPPORTED;
+  if ((rc = get_code(coding, k, m, w, c))) return rc;
+  if (!(*c)->bitmatrix) return LEOEC_E_UNSUPPORTED;
+  return locate_build_bitrows((*c)->B, k, m, w, rows);
+}
+
+int op_locate_bitrows(int coding, int k, int m, int w, uint32_t* rows, int cap) {
+  const Code* c;
+  std::vector<uint32_t> t;
+  const int rc = bit_locate_code(coding, k, m, w, &c, &t);
+  if (rc) return rc;
+  if (!rows || cap < (m - 1) * k * w) return LEOEC_E_ARG;
+  for (size_t i = 0; i < t.size(); ++i) rows[i] = t[i];
+  return LEOEC_OK;
+}
+
+int op_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                               uint64_t* bytes) {
+  uint64_t bs;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  const Code* c;
+  std::vector<uint32_t> t;
+  const bool bit = bit_class(coding);
+  if ((rc = bit ? bit_locate_code(coding, k, m, w, &c, &t) : locate_code(coding, k, m, w, &c, &t)))
+    return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  uint64_t per, all;
+  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
+    return LEOEC_E_BAD_SIZE;
+  *bytes = bit ? all : 0;
+  return LEOEC_OK;
+}
+
+int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                     uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+  uint64_t bs;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if (!bit_class(coding))  // served or LEOEC_E_UNSUPPORTED there; no workspace
+    return op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, lost,
+                         s);
+  const Code* c;
+  std::vector<uint32_t> rows;
+  if ((rc = bit_locate_code(coding, k, m, w, &c, &rows))) return rc;
+  if (nobj == 0 || bs == 0) return LEOEC_OK;
+  if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
+  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
+  if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per) return LEOEC_E_ARG;
+  if ((rc = device_init())) return rc;
+  std::vector<Shard> in(k);
+  std::vector<int> surv(k), want(m);
+  for (int j = 0; j < k; ++j) {
+    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
+    surv[j] = j;
+  }
+  for (int i = 0; i < m; ++i) want[i] = k + i;
+  std::shared_ptr<const Plan> plan;
+  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  BitLocArgs a;
+  a.ws = static_cast<const uint8_t*>(workspace);
+  a.parity_stride = parity_stride;
+  a.per = per;
+  a.ps = (uint32_t)(bs / (uint64_t)w);  // bs < 2^32 (check_dev_batch), a multiple of 16 w
+  a.tiles = (a.ps + kBitLocTile - 1u) / kBitLocTile;
+  a.k = (uint32_t)k;
+  a.m = (uint32_t)m;
+  a.w = (uint32_t)w;
+  for (size_t i = 0; i < (size_t)kBitLocWords; ++i) a.rows[i] = i < rows.size() ? rows[i] : 0u;
+  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
+  // no grid above 2^31 - 1 workgroups: bit_locate's, and verify_compare's
+  // bound, which keeps the encode plan's launches within theirs
+  const uint64_t cmp_tiles = (bs + kTileBytes - 1) / kTileBytes;
+  const uint64_t per_obj = a.tiles > (uint64_t)m * cmp_tiles ? a.tiles : (uint64_t)m * cmp_tiles;
+  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / per_obj;
+  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
+  if (chunk > max_obj) chunk = max_obj;
+  uint8_t* const ws = static_cast<uint8_t*>(workspace);
+  std::vector<Shard> enc(m);
+  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
+  const size_t lds = (size_t)w * kBitLocLanes * sizeof(u32x4);  // <= 32 KiB
+  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
+    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
+    std::vector<Shard> cin(in);
+    for (Shard& sh : cin) sh.base += o0 * obj_stride;
+    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
+    if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+    a.parity = parity + o0 * parity_stride;
+    hipLaunchKernelGGL(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s, a,
+                       lost + o0);
+    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    hipLaunchKernelGGL(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, lost + o0, (uint32_t)no);
+    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+  }
+  return LEOEC_OK;
+}
+
 }  // namespace
 }  // namespace leoec
 
 extern "C" {
+
+int leoec_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                  uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_locate_ws_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                        uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                        uint32_t* lost, void* workspace, uint64_t workspace_bytes, void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                   parity_stride, lost, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+  });
+}
+
+int leoec_locate_bitrows(int coding, int k, int m, int w, uint32_t* rows, int cap) {
+  return leoec::guarded([&] { return leoec::op_locate_bitrows(coding, k, m, w, rows, cap); });
+}
 
 int leoec_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
                      uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,

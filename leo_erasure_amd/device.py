@@ -193,6 +193,59 @@ def locate_rows(coding, params):
     return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
 
 
+def locate_ws_workspace(coding, params, size, nobj):
+    """leoec_locate_ws_dev_workspace: bytes of workspace locate_ws() wants for
+    one pass over the batch; 0 for everything locate() serves."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_locate_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
+                                                 ctypes.byref(out)))
+    return out.value
+
+
+def locate_ws(coding, params, objs, size, parity, nobj=None, lost=None, workspace=None,
+              stream=None):
+    """leoec_locate_ws_dev: locate()'s words, also for cauchyrs and liberation
+    (m >= 2, k + m <= 32, (m - 1) k w <= 768), which need a workspace.
+    ``workspace`` (uint8) follows verify()'s rules: allocated, up to
+    ``VERIFY_WORKSPACE_CAP``, when not given, and required on an explicit
+    ``stream``.  Returns ``lost``, which heal() takes as it is."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    if lost is None:
+        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    _words(lost, nobj, "lost")
+    need = locate_ws_workspace(coding, params, size, nobj)
+    if need and workspace is None:
+        if stream is not None:
+            raise ValueError("locate_ws on an explicit stream needs an explicit workspace "
+                             f"({need} B for one pass, at least {m * bs} B)")
+        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
+                                device=objs.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError("workspace: contiguous uint8 device tensor expected")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    _lib.check(lib.leoec_locate_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
+                                       size, nobj, parity.data_ptr(), _row_stride(parity),
+                                       lost.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
+    return lost
+
+
+def locate_bitrows(coding, params):
+    """leoec_locate_bitrows (no device needed): the GF(2) ratios locate_ws()
+    tests the syndromes of cauchyrs and liberation with: ``m - 1`` lists of k
+    lists of w row words, ``[i - 1][j][r]`` being row r of
+    T[i][j] = B[i][j] B[0][j]^-1 (bit c: syndrome packet c of coding block 0
+    feeds packet r of coding block i)."""
+    k, m, w = params
+    cap = max((m - 1) * k * w, 1)
+    rows = (ctypes.c_uint32 * cap)()
+    _lib.check(lib.leoec_locate_bitrows(_cid(coding), k, m, w, rows, cap))
+    return [[list(rows[((i * k) + j) * w:((i * k) + j + 1) * w]) for j in range(k)]
+            for i in range(m - 1)]
+
+
 def repair(coding, params, blocks, block_size, repair_ids, out, nobj, stream=None):
     """leoec_repair_dev.  ``blocks``: list of k+m tensors-or-None, each
     ``[nobj, stride]`` with the block at byte 0 of every row (all the same
