@@ -12,6 +12,7 @@ one oracle-encoded object, must give exactly the lost blocks, and the record
 indices must be a bijection onto 0..N-1: a wrong rank or a wrong row here is
 a wrong block on the device."""
 import ctypes
+import math
 
 import numpy as np
 import pytest
@@ -153,6 +154,40 @@ def test_heal_rows_fused(le, oracle, cfg, count):
     a bijection onto 0..N-1, the survivors are the first k intact ids, and
     the rows rebuild the lost blocks of an oracle-encoded object."""
     _check_rows(le, oracle, cfg, True, count)
+
+
+def _rank(k, m, mask):
+    """heal_table.hpp's record index, restated: first[p] + sum of C(b_i, i)
+    over the set bits b_1 < ... < b_p, first[p] = sum of C(k + m, q), q < p."""
+    ids = P.ids_of(mask)
+    return (sum(math.comb(k + m, q) for q in range(1, len(ids))) +
+            sum(math.comb(b, i) for i, b in enumerate(ids, 1)))
+
+
+@pytest.mark.parametrize("cls", ["vandrs", "isars"])
+def test_heal_rows_every_fused_configuration(le, oracle, cls):
+    """k = 1..16 x m = 1..4, all 64 configurations of the class (one gf8_heal
+    table each): every single-block mask and the cyclic runs of m blocks from
+    every block.  The rows rebuild the lost 256-byte blocks of an
+    oracle-encoded object, and the record index is the combinatorial rank.
+    This pins the table contents of the configurations whose gf8_heal launch
+    no device test runs (tests/gf8_heal_instances_child.py heals 32 of them)."""
+    for k in range(1, 17):
+        for m in range(1, 5):
+            n = k + m
+            blocks = _one_object(le, oracle, cls, k, m, 8)
+            assert len(blocks[0]) == 256
+            masks = [1 << b for b in range(n)]
+            masks += [P.bits((b + x) % n for x in range(m)) for b in range(n)]
+            for mask in dict.fromkeys(masks):
+                surv, want, rows, index = le.device.heal_rows(cls, (k, m, 8), mask)
+                lost = P.ids_of(mask)
+                assert want == lost and len(rows) == len(lost), (cls, k, m, hex(mask))
+                assert surv == [b for b in range(n) if b not in lost][:k], (cls, k, m, hex(mask))
+                assert index == _rank(k, m, mask), (cls, k, m, hex(mask), index)
+                got = P.apply_rows(oracle, cls, 8, rows, [blocks[s] for s in surv])
+                for b, g in zip(lost, got):
+                    assert np.array_equal(g, blocks[b]), f"{cls}({k},{m}) mask {mask:#x}: block {b}"
 
 
 @pytest.mark.parametrize("cfg,count", [(("cauchyrs", 6, 3, 4), 9 + 36 + 84),
