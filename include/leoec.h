@@ -288,6 +288,64 @@ int leoec_locate_ws_dev(int coding, int k, int m, int w, const uint8_t *objs, ui
                         uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
                         uint32_t *lost, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* Workspace bytes leoec_scrub_dev needs for nobj objects:
+ * 16 + round_up(4 * nobj, 16), a header and one index word per object;
+ * LEOEC_E_BAD_SIZE when that overflows; bytes == NULL: LEOEC_E_ARG.
+ * Configurations leoec_scrub_dev does not serve, and invalid ones, get its
+ * statuses.  Needs no device. */
+int leoec_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                              uint64_t *bytes);
+
+/* Scrub a stored batch in one call: find the inconsistent objects, name the
+ * damaged block of each, rebuild it in place and count what was found, all on
+ * the device.  The contract is the composition leoec_locate_dev then
+ * leoec_heal_dev(lost = report): after the call
+ *   report[o]  is leoec_locate_dev's word for object o of the batch as it was
+ *              before the call: 0, one bit b < k + m, or LEOEC_LOCATE_MANY;
+ *   objs and parity hold the bytes leoec_heal_dev(..., lost = report, ...)
+ *              leaves: every object whose word names one block has that block
+ *              rebuilt in place from its first k intact ids ascending, data
+ *              blocks clipped to `size`, bytes past `size` read as zero and
+ *              never touched; a clean object and a LEOEC_LOCATE_MANY object
+ *              are not written at all;
+ *   totals[0]  is the number of objects named and rebuilt, totals[1] the number
+ *              of LEOEC_LOCATE_MANY objects; both words are overwritten, so 8
+ *              bytes tell whether the batch was clean.
+ * Layout, alignment and stride rules are those of leoec_verify_dev and
+ * leoec_heal_dev.  report: device, 4-byte aligned, nobj words, every one
+ * overwritten.  totals: device, 4-byte aligned, 2 words.  workspace: device,
+ * 16-byte aligned, at least leoec_scrub_dev_workspace's bytes; its contents
+ * after the call are unspecified.  report, totals or workspace NULL or
+ * misaligned, report or totals inside the workspace, or workspace_bytes below
+ * the query's: LEOEC_E_ARG.
+ * Served: what leoec_locate_dev serves, vandrs w = 8 and isars with k <= 16
+ * and 2 <= m <= 4.  Everything else (cauchyrs and liberation included: they
+ * would need leoec_locate_ws_dev and a synchronising heal) is
+ * LEOEC_E_UNSUPPORTED, returned before the device is opened; invalid
+ * parameters keep their leoec_check_params status; nobj == 0 is LEOEC_OK with
+ * nothing written.  The checks come in leoec_locate_dev's order: layout and
+ * parameters, served, empty batch, pointers and strides, then the device.
+ * The limit at m = 2 is leoec_locate_dev's: with m >= 3 two damaged blocks are
+ * never taken for one, with m = 2 they may be reported as a third block, which
+ * is then "healed": the stripe is left consistent but wrong.
+ * What runs: per chunk of objects leoec_locate_dev's memset and launch, one
+ * launch that writes the final words and lists the objects that name a block,
+ * and one launch of fixed size that rebuilds the listed objects' blocks, so
+ * the repair costs by the number of damaged objects, not by the batch.
+ * The call allocates nothing, uploads nothing and never synchronises, so it
+ * can be captured into a graph, after the first call: the first call of a
+ * code on a device builds and uploads leoec_heal_dev's pattern table (up to
+ * 8 MB, a blocking copy) and loads the code objects (1-2 ms each); the
+ * leoec_gf_init warm-up does not cover them.  The table cache holds 16 tables
+ * per process; past that the call runs leoec_locate_dev then leoec_heal_dev's
+ * other path, which brings the masks back to the host (one stream
+ * synchronisation), rebuilds runs of consecutive objects with the same mask
+ * and fills the workspace's index words from the host. */
+int leoec_scrub_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                    uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                    uint32_t *report, uint32_t *totals, void *workspace, uint64_t workspace_bytes,
+                    void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
 
 /* The GF(2) ratios leoec_locate_ws_dev tests the syndromes of cauchyrs and

@@ -44,7 +44,7 @@ EXPORTS = (
     "leoec_coding_matrix", "leoec_device", "leoec_host_lanes", "leoec_host_spread",
     "leoec_version", "leoec_verify_dev_workspace", "leoec_verify_dev", "leoec_heal_dev",
     "leoec_heal_rows", "leoec_locate_dev", "leoec_locate_rows", "leoec_locate_ws_dev_workspace",
-    "leoec_locate_ws_dev", "leoec_locate_bitrows",
+    "leoec_locate_ws_dev", "leoec_locate_bitrows", "leoec_scrub_dev_workspace", "leoec_scrub_dev",
 )
 
 
@@ -105,6 +105,8 @@ def _load(path=LIB_PATH):
     L.leoec_locate_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
     L.leoec_locate_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
     L.leoec_locate_bitrows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
+    L.leoec_scrub_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
+    L.leoec_scrub_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

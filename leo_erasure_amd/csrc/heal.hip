@@ -24,6 +24,7 @@
 #include "engine.hpp"
 #include "heal_impl.hpp"
 #include "knobs.hpp"
+#include "scrub_steps.hpp"
 
 namespace leoec {
 
@@ -48,6 +49,8 @@ struct HealTable {
   std::vector<uint32_t> host;
   uint32_t* dev = nullptr;
 };
+
+}  // namespace
 
 // LEOEC_OK and *out = the device image, or *out = nullptr when the cache is
 // full; a status when the build or the upload failed.
@@ -84,6 +87,8 @@ int heal_table(const Code& c, const uint32_t** out) {
   cache->emplace(key, std::move(t));
   return LEOEC_OK;
 }
+
+namespace {
 
 bool recoverable(uint32_t mask, int k, int m) {
   return __builtin_popcount(mask) <= m && ((uint64_t)mask >> (k + m)) == 0;
@@ -137,6 +142,8 @@ int heal_generic(const Code& c, uint8_t* objs, uint64_t obj_stride, uint64_t siz
   return LEOEC_OK;
 }
 
+}  // namespace
+
 int op_heal_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride, uint64_t size,
                 uint64_t nobj, uint8_t* parity, uint64_t parity_stride, const uint32_t* lost,
                 uint32_t* unhealed, hipStream_t s) {
@@ -179,6 +186,8 @@ int op_heal_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_str
   }
   return LEOEC_OK;
 }
+
+namespace {
 
 int op_heal_rows(int coding, int k, int m, int w, uint32_t lost_mask, int* surv, int* want,
                  int* nwant, uint32_t* coef, int cap, int* index) {

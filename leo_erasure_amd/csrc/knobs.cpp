@@ -117,6 +117,7 @@ const Knobs* read_env() {
   k->gfs_pf = env_int("LEOEC_GFS_PF", k->gfs_pf);
   k->verify_form = env_int("LEOEC_VERIFY_FORM", k->verify_form);
   k->heal_form = env_int("LEOEC_HEAL_FORM", k->heal_form);
+  k->scrub_grid = env_int("LEOEC_SCRUB_GRID", k->scrub_grid);
   return k;
 }
 

@@ -124,6 +124,9 @@ struct Knobs {
   int heal_form = 0;         // LEOEC_HEAL_FORM=1: leoec_heal_dev always through the generic path
                              //   (masks copied back, one plan launch per run of equal masks),
                              //   also where gf8_heal would serve
+  // scrub.hip
+  int scrub_grid = 0;        // LEOEC_SCRUB_GRID=n: gf8_heal_list's grid capped at n workgroups
+                             //   (the persistent loop at test-sized batches; 0: the shipped grid)
 };
 
 const Knobs& knobs();

@@ -20,6 +20,8 @@
 //                   packet form of the test (locate_bitrows.hpp);
 //   locate_finish.
 // Everything leoec_locate_dev serves is forwarded to it.
+// leoec_scrub_dev (scrub.hip) runs op_locate_dev with its own steps in it
+// (scrub_steps.hpp): its kernel stands in locate_finish's place.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
@@ -30,6 +32,7 @@
 #include "locate_bitrows.hpp"
 #include "locate_impl.hpp"
 #include "locate_rows.hpp"
+#include "scrub_steps.hpp"
 
 namespace leoec {
 
@@ -75,9 +78,13 @@ int op_locate_rows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
   return LEOEC_OK;
 }
 
+}  // namespace
+
+// steps (scrub_steps.hpp): leoec_scrub_dev's share of the call; none for
+// leoec_locate_dev itself.
 int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
                   uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
-                  uint32_t* lost, hipStream_t s) {
+                  uint32_t* lost, hipStream_t s, LocateSteps* steps) {
   uint64_t bs;
   int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
   if (rc) return rc;
@@ -86,8 +93,10 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   if ((rc = locate_code(coding, k, m, w, &c, &ratio))) return rc;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
   if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if (steps && (rc = steps->check(bs))) return rc;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   if ((rc = device_init())) return rc;
+  if (steps && (rc = steps->begin(*c, s))) return rc;
   GfApply a;
   a.w = w;
   a.K = k;
@@ -107,6 +116,10 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     const uint64_t no = nobj - o0 < max_obj ? nobj - o0 : max_obj;
     if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
     if ((rc = fn(a, ratio.data(), o0, no, lost, s))) return rc;
+    if (steps) {
+      if ((rc = steps->finish(o0, no, s))) return rc;
+      continue;
+    }
     // no <= 2^31 - 1 words: one grid
     hipLaunchKernelGGL(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, s, lost + o0, (uint32_t)no);
@@ -114,6 +127,8 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   }
   return LEOEC_OK;
 }
+
+namespace {
 
 // ---------------------------------------------------------------------------
 // The bitmatrix classes: leoec_locate_ws_dev.
@@ -261,7 +276,7 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
   if (rc) return rc;
   if (!bit_class(coding))  // served or LEOEC_E_UNSUPPORTED there; no workspace
     return op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, lost,
-                         s);
+                         s, nullptr);
   const Code* c;
   std::vector<uint32_t> rows;
   if ((rc = bit_locate_code(coding, k, m, w, &c, &rows))) return rc;
@@ -349,7 +364,7 @@ int leoec_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
                      uint32_t* lost, void* stream) {
   return leoec::guarded([&] {
     return leoec::op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
-                                parity_stride, lost, (hipStream_t)stream);
+                                parity_stride, lost, (hipStream_t)stream, nullptr);
   });
 }
 

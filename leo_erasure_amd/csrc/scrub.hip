@@ -1,0 +1,222 @@
+// scrub.hip — leoec_scrub_dev: find the inconsistent objects of a device
+// batch, name the damaged block of each and rebuild it in place, in one call
+// and without a host round trip: leoec_locate_dev's words and leoec_heal_dev's
+// bytes, at a cost that follows the number of damaged objects.
+//
+// Served: what leoec_locate_dev serves.  Per chunk of objects (gf8_max_objects),
+// on the stream, nothing allocated, uploaded or waited for:
+//   locate          op_locate_dev's memset + gf8_locate (locate.hip), with
+//   scrub_finish    below in locate_finish's place: the final word of every
+//                   object, the indices of the objects that name one block
+//                   appended to a list in the workspace (header word 0: their
+//                   count), both totals added to;
+//   gf8_heal_list   (scrub_impl.hpp) gf8_heal's tile over that list from a
+//                   fixed grid.
+// Workspace: a 16-byte header, then one index word per object.
+// When heal's table cache is full (heal.hip) the call is the composition
+// itself: op_locate_dev with scrub_finish counting only, then op_heal_dev's
+// generic path with the index words as its `unhealed`, which synchronises once.
+// This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
+// host sanitizer harness links those against stand-in kernels.  The gf_init
+// warm-up does not load this unit's kernels either.
+#include <utility>
+
+#include "engine.hpp"
+#include "knobs.hpp"
+#include "scrub_impl.hpp"
+#include "scrub_steps.hpp"
+
+namespace leoec {
+
+using namespace detail;
+
+namespace {
+
+constexpr uint64_t kScrubHeader = 16;  // bytes; word 0: the chunk's count
+
+template <std::size_t... I>
+HealListFn gf8_heal_list_pick(std::index_sequence<I...>, int k) {
+  static HealListFn (*const sel[])() = {&gf8_heal_list_launcher<(int)I + 1>...};
+  return sel[k - 1]();
+}
+
+// locate_finish (locate.hip) with the compaction in it.  One word per lane, in
+// place: all ones -> 0, exactly one bit -> kept, anything else ->
+// LEOEC_LOCATE_MANY.  A wave with single-bit words takes its stretch of the
+// list with one atomicAdd on *count (list != nullptr) and adds their number to
+// totals[0] with another; one with LEOEC_LOCATE_MANY words adds theirs to
+// totals[1].  A wave with neither issues no atomic: a clean batch writes its
+// words and nothing else.  No lane leaves early: lanes past n hold a clean
+// word, so lane 0 is there to issue the wave's atomics.  The order of the list
+// is whatever order the waves arrive in.
+__global__ void __launch_bounds__(kThreads)
+scrub_finish(uint32_t* __restrict__ words, uint32_t n, uint32_t* __restrict__ list,
+             uint32_t* __restrict__ count, uint32_t* __restrict__ totals) {
+  const uint32_t i = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
+  const bool in = i < n;
+  const uint32_t v = in ? words[i] : 0xFFFFFFFFu;
+  const uint32_t f = v == 0xFFFFFFFFu ? 0u : (v != 0u && (v & (v - 1u)) == 0u) ? v : LEOEC_LOCATE_MANY;
+  if (in) words[i] = f;
+  // (with k + m <= 20 no single-bit word is LEOEC_LOCATE_MANY's own bit)
+  const bool many = f == LEOEC_LOCATE_MANY;
+  const bool one = f != 0u && !many;
+  const uint64_t b1 = __builtin_amdgcn_ballot_w64(one);
+  const uint64_t bm = __builtin_amdgcn_ballot_w64(many);
+  if ((b1 | bm) == 0ull) return;  // wave-uniform
+  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if (b1 != 0ull) {
+    const uint32_t c = (uint32_t)__builtin_popcountll(b1);
+    uint32_t base = 0;
+    if (lane == 0u) {
+      if (list) base = atomicAdd(count, c);
+      atomicAdd(&totals[0], c);
+    }
+    base = __builtin_amdgcn_readfirstlane(base);
+    // the lane's rank among the wave's single-bit lanes
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
+    if (list && one) list[base + rank] = i;
+  }
+  if (bm != 0ull && lane == 0u) atomicAdd(&totals[1], (uint32_t)__builtin_popcountll(bm));
+}
+
+// Bytes of workspace for nobj objects; false when that overflows.
+bool scrub_workspace(uint64_t nobj, uint64_t* bytes) {
+  uint64_t words;
+  if (__builtin_mul_overflow(nobj, (uint64_t)sizeof(uint32_t), &words) ||
+      __builtin_add_overflow(words, (uint64_t)15, &words))
+    return false;
+  return !__builtin_add_overflow(words & ~(uint64_t)15, kScrubHeader, bytes);
+}
+
+// [p, p + n) meets [q, q + qn) (no sum that could wrap).
+bool overlaps(const void* p, uint64_t n, const void* q, uint64_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a >= b ? a - b < qn : b - a < n;
+}
+
+int op_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                           uint64_t* bytes) {
+  // leoec_locate_dev's statuses, none of which needs a device: an empty batch
+  // with no buffers goes through its parameter and served tests and ends there
+  const int rc = op_locate_dev(coding, k, m, w, nullptr, 0, size, 0, nullptr, 0, nullptr, nullptr,
+                               nullptr);
+  if (rc) return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  return scrub_workspace(nobj, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
+}
+
+// leoec_scrub_dev's share of op_locate_dev.
+struct ScrubSteps final : LocateSteps {
+  int k = 0, m = 0;
+  uint8_t* objs = nullptr;
+  uint64_t obj_stride = 0, size = 0, bs = 0, nobj = 0;
+  uint8_t* parity = nullptr;
+  uint64_t parity_stride = 0;
+  uint32_t* report = nullptr;
+  uint32_t* totals = nullptr;
+  void* workspace = nullptr;
+  uint64_t workspace_bytes = 0;
+  bool begun = false;               // begin() ran: the device is open
+  const uint32_t* table = nullptr;  // heal's; nullptr after begin(): its cache is full
+  HealListFn heal = nullptr;
+
+  uint32_t* header() const { return static_cast<uint32_t*>(workspace); }
+  uint32_t* list() const { return header() + kScrubHeader / sizeof(uint32_t); }
+
+  int check(uint64_t block_size) override {
+    bs = block_size;
+    if (!totals || ((uintptr_t)totals & 3u)) return LEOEC_E_ARG;
+    if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
+    uint64_t need;
+    if (!scrub_workspace(nobj, &need)) return LEOEC_E_BAD_SIZE;
+    if (workspace_bytes < need) return LEOEC_E_ARG;
+    if (overlaps(report, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
+        overlaps(totals, 2 * sizeof(uint32_t), workspace, workspace_bytes))
+      return LEOEC_E_ARG;
+    return LEOEC_OK;
+  }
+
+  int begin(const Code& c, hipStream_t s) override {
+    const int rc = heal_table(c, &table);
+    if (rc) return rc;
+    begun = true;
+    heal = gf8_heal_list_pick(std::make_index_sequence<kMaxK>{}, k);
+    return hipMemsetAsync(totals, 0, 2 * sizeof(uint32_t), s) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  }
+
+  int finish(uint64_t o0, uint64_t no, hipStream_t s) override {
+    uint32_t* const words = report + o0;
+    if (table && hipMemsetAsync(header(), 0, kScrubHeader, s) != hipSuccess) return LEOEC_E_HIP;
+    // no <= 2^31 - 1 words: one grid
+    hipLaunchKernelGGL(scrub_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, words, (uint32_t)no, table ? list() : nullptr, header(),
+                       totals);
+    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (!table) return LEOEC_OK;
+    HealArgs a;
+    a.objs = objs + o0 * obj_stride;
+    a.obj_stride = obj_stride;
+    a.parity = parity + o0 * parity_stride;
+    a.parity_stride = parity_stride;
+    a.lost = words;
+    a.unhealed = nullptr;
+    a.table = table;
+    a.size = size;
+    a.bs = (uint32_t)bs;
+    a.k = (uint32_t)k;
+    a.m = (uint32_t)m;
+    a.nobj = (uint32_t)no;
+    a.tiles = a.tmap = a.tperm = 0;  // the launcher's
+    const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
+    return heal(a, list(), header(), cap, s);
+  }
+};
+
+int op_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride, uint64_t size,
+                 uint64_t nobj, uint8_t* parity, uint64_t parity_stride, uint32_t* report,
+                 uint32_t* totals, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+  ScrubSteps st;
+  st.k = k;
+  st.m = m;
+  st.objs = objs;
+  st.obj_stride = obj_stride;
+  st.size = size;
+  st.nobj = nobj;
+  st.parity = parity;
+  st.parity_stride = parity_stride;
+  st.report = report;
+  st.totals = totals;
+  st.workspace = workspace;
+  st.workspace_bytes = workspace_bytes;
+  const int rc = op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+                         report, s, &st);
+  if (rc || !st.begun || st.table) return rc;
+  // heal's table cache is full: the words are final and counted; the rest is
+  // leoec_heal_dev's generic path (one synchronisation)
+  return op_heal_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                     st.list(), s);
+}
+
+}  // namespace
+}  // namespace leoec
+
+extern "C" {
+
+int leoec_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                              uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_scrub_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                    uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                    uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
+                    void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_scrub_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+                               report, totals, workspace, workspace_bytes, (hipStream_t)stream);
+  });
+}
+
+}  // extern "C"

@@ -232,6 +232,48 @@ def locate_ws(coding, params, objs, size, parity, nobj=None, lost=None, workspac
     return lost
 
 
+def scrub_workspace(coding, params, size, nobj):
+    """leoec_scrub_dev_workspace: bytes of workspace scrub() needs for ``nobj``
+    objects (a 16-byte header and one index word per object)."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_scrub_dev_workspace(_cid(coding), k, m, w, size, nobj, ctypes.byref(out)))
+    return out.value
+
+
+def scrub(coding, params, objs, size, parity, nobj=None, report=None, totals=None, workspace=None,
+          stream=None):
+    """leoec_scrub_dev: locate() then heal() in one call, without a host round
+    trip and at a cost that follows the number of damaged objects.  Returns
+    ``(report, totals)``: ``report`` (int32, ``nobj`` words) holds locate()'s
+    words for the batch as it was, ``objs`` and ``parity`` the bytes
+    ``heal(..., lost=report)`` leaves, ``totals`` (int32, 2 words) the number of
+    objects named and rebuilt and the number of ``LOCATE_MANY`` objects.
+    ``report``, ``totals`` and ``workspace`` (uint8, at least
+    ``scrub_workspace()`` bytes) are allocated when not given; a call on an
+    explicit ``stream`` must be given the workspace, for verify()'s reason.
+    vandrs w = 8 and isars with k <= 16, 2 <= m <= 4."""
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
+    if report is None:
+        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    if totals is None:
+        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
+    _words(report, nobj, "report")
+    _words(totals, 2, "totals")
+    need = scrub_workspace(coding, params, size, nobj)
+    if workspace is None:
+        if stream is not None:
+            raise ValueError(f"scrub on an explicit stream needs an explicit workspace ({need} B)")
+        workspace = torch.empty(need, dtype=torch.uint8, device=objs.device)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    _lib.check(lib.leoec_scrub_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                   nobj, parity.data_ptr(), _row_stride(parity), report.data_ptr(),
+                                   totals.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                   _stream(stream)))
+    return report, totals
+
+
 def locate_bitrows(coding, params):
     """leoec_locate_bitrows (no device needed): the GF(2) ratios locate_ws()
     tests the syndromes of cauchyrs and liberation with: ``m - 1`` lists of k

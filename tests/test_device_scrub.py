@@ -1,0 +1,173 @@
+"""leoec_scrub_dev on the device (product library): locate and heal in one
+call, on the edge harness of gpu_helpers (guarded arenas, random non-zero
+bytes behind every object, every byte of both arenas, the words around the
+covered ones and the workspace's tail compared after every call).
+
+The contract is the composition device.locate then device.heal(lost = report);
+the batches are scrub_helpers' position batch (object b of k + m + 2 has block
+b damaged, one object is clean, one has two damaged blocks), a clean batch and
+a dense batch (object o has block o mod (k + m) damaged), for the six families
+of locate_helpers.FAMILIES (the fused configurations at 256 lanes, the 64-lane
+tiles, K = 16) at the sizes k B - 1 and 16 w (k - 2) + 5.  Expected words are
+by construction (scrub_helpers.position_batch, held against the oracle and the
+host model by test_device_scrub_positions.py's CPU test)."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+import gpu_helpers as H
+import locate_helpers as L
+import scrub_dev_helpers as D
+import scrub_helpers as S
+
+
+@pytest.fixture(scope="module", params=L.FAMILIES, ids=L.family_id)
+def family(request):
+    """(module scope: the tests of one family run together and share its
+    EdgeCases, the oracle's blocks computed once per size)"""
+    return request.param
+
+
+def test_family_table():
+    assert len(L.FAMILIES) == 6
+    assert ("vandrs", 10, 4, 8, 164992) in L.FAMILIES and ("vandrs", 16, 4, 8, 8704) in L.FAMILIES
+    assert any(f[2] == 2 for f in L.FAMILIES)  # the m = 2 limit is met
+
+
+@pytest.mark.gpu
+def test_device_scrub_positions(gpu, le, oracle, family):
+    """One scrub of the position batch: the by-construction report between
+    intact sentinels, totals, every named object back to the snapshot, the
+    two-block object untouched.  Then the same damage through device.locate +
+    device.heal: identical arenas and words, no object left out.  Then a second
+    scrub of the healed arenas: all zero but for the two-block object, nothing
+    rebuilt, no byte changed."""
+    cls, k, m, w, B = family
+    errors = []
+    for case in D.position_cases(le, oracle, family):
+        dmg, _, locate = S.position_batch(case)
+        want = S.two_block_word(oracle, le, case, dmg, locate)
+        skip = None if want[-1] == S.MANY else case.n - 1
+        assert skip is None or m == 2
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        errors += D.check_scrub(gpu, le, case, work, par, want, skip)[1]
+        work, par, got, errs = D.check_equivalence(gpu, le, case, dmg)
+        errors += errs
+        if got != want:
+            errors.append(f"{case.ident()}: equivalence run's report {[hex(x) for x in got]}")
+        # the healed arenas again
+        healed, par_healed = work.clone(), par.clone()
+        _, again, tot, errs = D.run_scrub(gpu, le, case, work, par)
+        errors += errs
+        ctx = f"second scrub {case.ident()} bs {case.bs}"
+        # (m = 2 with a third block named: the other k + 1 blocks fit one
+        # another, so the rebuilt stripe is consistent, if wrong)
+        many = 1 if want[-1] == S.MANY else 0
+        expect = [0] * (case.n - 1) + [S.MANY if many else 0]
+        if again != expect or tot != [0, many]:
+            errors.append(f"{ctx}: report {[hex(x) for x in again]}, totals {tot}, expected "
+                          f"{[hex(x) for x in expect]}, {[0, many]}")
+        for err in (H.arena_diff(gpu, work, healed, case.guard, f"{ctx}: objs"),
+                    H.arena_diff(gpu, par, par_healed, 1, f"{ctx}: parity")):
+            if err:
+                errors.append(err)
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_clean_batch(gpu, le, oracle, family):
+    """Nothing damaged: every word 0, totals (0, 0), no byte written."""
+    errors = []
+    for case in D.position_cases(le, oracle, family):
+        work, par = L.damaged_arenas(gpu, case, [])
+        errors += D.check_scrub(gpu, le, case, work, par, [0] * case.n)[1]
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_dense_batch(gpu, le, oracle, family):
+    """Every object with one damaged block, object o block o mod (k + m): every
+    one named and rebuilt, and the two-call sequence leaves the same bytes."""
+    errors = []
+    for case in D.position_cases(le, oracle, family):
+        dmg, want = D.dense_batch(case)
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        errors += D.check_scrub(gpu, le, case, work, par, want)[1]
+        errors += D.check_equivalence(gpu, le, case, dmg)[3]
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_captured(gpu, le, oracle):
+    """The call is memsets and launches on the stream, a linear chain: captured
+    into a graph (after one plain call, which builds heal's table and loads
+    the code objects) it replays to the same report, totals and arenas, and
+    again after the buffers are refilled with a differently damaged batch."""
+    family = L.FAMILIES[0]
+    cls, k, m, w, B = family
+    case = next(iter(D.position_cases(le, oracle, family)))
+    n, g = case.n, case.guard
+    snap, par_snap = case.dev(gpu)
+    dmg, _, locate = S.position_batch(case)
+    want = S.two_block_word(oracle, le, case, dmg, locate)
+    assert want[-1] == S.MANY  # m >= 3: every word by construction
+    first, par_first = L.damaged_arenas(gpu, case, dmg)
+    work, par = first.clone(), par_first.clone()
+    errors = D.check_scrub(gpu, le, case, work, par, want)[1]
+    assert not errors, "\n".join(errors)
+
+    def expect(before, par_before, words):
+        o_want, p_want = snap.clone(), par_snap.clone()
+        for o, word in enumerate(words):
+            if word == S.MANY:
+                o_want[g + o], p_want[1 + o] = before[g + o], par_before[1 + o]
+        return o_want, p_want, [sum(1 for x in words if x not in (0, S.MANY)),
+                                sum(1 for x in words if x == S.MANY)]
+
+    work.copy_(first)
+    par.copy_(par_first)
+    report = gpu.full((n,), L.PREFILL, dtype=gpu.int32, device="cuda")
+    totals = gpu.full((2,), D.TOTALS_PREFILL, dtype=gpu.int32, device="cuda")
+    need = le.device.scrub_workspace(cls, case.params, case.size, n)
+    ws = gpu.full((need,), D.WS_FILL, dtype=gpu.uint8, device="cuda")
+    gpu.cuda.synchronize()
+    graph = gpu.cuda.CUDAGraph()
+    with gpu.cuda.graph(graph):
+        le.device.scrub(cls, case.params, work[g:g + n], case.size, par[1:1 + n], report=report,
+                        totals=totals, workspace=ws)
+    dense, dense_words = D.dense_batch(case)
+    second, par_second = L.damaged_arenas(gpu, case, dense)
+    for before, par_before, words in ((first, par_first, want), (second, par_second, dense_words),
+                                      (first, par_first, want)):
+        work.copy_(before)
+        par.copy_(par_before)
+        report.fill_(L.PREFILL)
+        totals.fill_(D.TOTALS_PREFILL)
+        graph.replay()
+        gpu.cuda.synchronize()
+        o_want, p_want, counts = expect(before, par_before, words)
+        assert D._u32(report) == words, [hex(x) for x in D._u32(report)]
+        assert D._u32(totals) == counts
+        assert not H.arena_diff(gpu, work, o_want, g, "replay: objs")
+        assert not H.arena_diff(gpu, par, p_want, 1, "replay: parity")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_scrub_with_full_table_cache_in_own_process(gpu, tmp_path):
+    """tests/scrub_table_cache_child.py in a fresh process: 16 configurations
+    healed first fill heal's table cache, the scrub of a 17th then takes the
+    composed path and must still equal locate + heal byte for byte."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log = str(tmp_path / "scrub_table_cache.log")
+    env = dict(os.environ, LIBC_FATAL_STDERR_="1")
+    env.pop("LEOEC_LIBRARY", None)
+    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_table_cache_child.py")]
+    with open(log, "w") as fh:
+        rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=280)
+    with open(log) as fh:
+        tail = fh.read()[-4000:]
+    assert rc == 0, f"scrub_table_cache_child.py failed (rc {rc}), {log}:\n{tail}"
+    assert "17th configuration scrubbed" in tail, tail
