@@ -17,7 +17,21 @@
  *   - reentrant and thread-safe: concurrent callers (the basho_bench t4
  *     configuration) each get their own HIP stream and staging buffers;
  *   - the GF arithmetic always runs on the GPU (HIP, gfx950); a missing or
- *     unusable device is reported as LEOEC_E_NO_DEVICE, never computed on CPU.
+ *     unusable device is reported as LEOEC_E_NO_DEVICE, never computed on CPU;
+ *   - a call's status reflects only that call's own work.  HIP keeps one
+ *     sticky last-error slot per thread (hipGetLastError /
+ *     hipPeekAtLastError), shared with the caller's own HIP code:
+ *       . an error pending on the calling thread before the call is never
+ *         reported as the call's failure;
+ *       . a call that returns LEOEC_OK and found the thread's last-error slot
+ *         clean leaves it clean (a HIP failure the library recovers from is
+ *         dropped from the slot);
+ *       . a *_dev call in which no HIP call of its own fails leaves the
+ *         caller's pending error in place: hipPeekAtLastError shows the same
+ *         code before and after;
+ *       . a call that fails with LEOEC_E_HIP or LEOEC_E_NOMEM may leave its
+ *         own failed HIP call's code in the slot; a host-memory call that
+ *         recovers from a failure clears the slot, whatever was pending.
  */
 #ifndef LEOEC_H
 #define LEOEC_H

@@ -228,8 +228,7 @@ int launch_cbm_t(const GfBitApply& p, hipStream_t s) {
   a.xmap = (a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
   const uint64_t grid = p.nobj * a.tiles;
   if (grid == 0 || grid > 0x7FFFFFFFull) return LEOEC_E_ARG;
-  hipLaunchKernelGGL((cbm_apply<BM, TW, WAVES, D>), dim3((uint32_t)grid), dim3(TW), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((cbm_apply<BM, TW, WAVES, D>), dim3((uint32_t)grid), dim3(TW), 0, s, a);
 }
 
 // the plan's coefficient rows are the compiled matrix's (encode)

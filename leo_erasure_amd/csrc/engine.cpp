@@ -470,7 +470,7 @@ int device_init() {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return;
     for (int d = 0; d < n && d < kMaxDevices; ++d) {
       hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, d) != hipSuccess) continue;
+      if (!hip_drop(hipGetDeviceProperties(&prop, d))) continue;  // (a device passed over)
       if (std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) g_host_devices.push_back(d);
     }
     if (!g_host_devices.empty()) status = LEOEC_OK;
@@ -498,7 +498,7 @@ DeviceScope::DeviceScope(int dev) {
 }
 
 DeviceScope::~DeviceScope() {
-  if (prev_ >= 0) (void)hipSetDevice(prev_);
+  if (prev_ >= 0) hip_drop(hipSetDevice(prev_));
 }
 
 namespace {
@@ -637,15 +637,20 @@ void reclaim_drain() {
   }
   for (Reclaim& r : todo) {
     DeviceScope on(r.device);
+    // (a device that cannot be made current: the frees below are attempted
+    // all the same, and whatever fails here is no caller's error)
+    if (!on.ok()) (void)hipGetLastError();
     if (hipStreamQuery(r.stream) != hipSuccess) {
-      (void)hipGetLastError();  // (not-ready is not an error of any call)
+      // drops hipStreamQuery's own status: not-ready is not an error of any
+      // call, and a failed query is this drain's, not the caller's
+      (void)hipGetLastError();
       g_reclaim_busy.fetch_add(1, std::memory_order_relaxed);
-      (void)hipStreamSynchronize(r.stream);
+      hip_drop(hipStreamSynchronize(r.stream));
     }
-    for (hipEvent_t e : r.events) (void)hipEventDestroy(e);
-    if (r.buf) (void)hipFree(r.buf);
-    if (r.ring) (void)hipHostFree(r.ring);
-    if (r.hbuf) (void)hipHostFree(r.hbuf);
+    for (hipEvent_t e : r.events) hip_drop(hipEventDestroy(e));
+    if (r.buf) hip_drop(hipFree(r.buf));
+    if (r.ring) hip_drop(hipHostFree(r.ring));
+    if (r.hbuf) hip_drop(hipHostFree(r.hbuf));
     ResourcePool& p = g_pool[r.device];
     bool pooled = false;
     {
@@ -656,7 +661,7 @@ void reclaim_drain() {
         pooled = true;
       }
     }
-    if (r.mapped.h && !pooled) (void)hipHostFree(r.mapped.h);
+    if (r.mapped.h && !pooled) hip_drop(hipHostFree(r.mapped.h));
     g_reclaim_drained.fetch_add(1, std::memory_order_relaxed);
   }
 }
@@ -701,14 +706,14 @@ uint8_t* gather_buf(Staging* st, size_t bytes) {
   if (bytes == 0 || bytes > kGatherMax) return nullptr;
   if (st->hcap >= bytes) return st->hbuf;
   if (st->hbuf) {
-    (void)hipStreamSynchronize(st->stream);
-    (void)hipHostFree(st->hbuf);
+    hip_drop(hipStreamSynchronize(st->stream));
+    hip_drop(hipHostFree(st->hbuf));
     st->hbuf = nullptr;
     st->hcap = 0;
   }
   const size_t want = std::max<size_t>(bytes + bytes / 4, (size_t)2 << 20);
-  if (hipHostMalloc((void**)&st->hbuf, want, hipHostMallocDefault) != hipSuccess) {
-    st->hbuf = nullptr;
+  if (!hip_drop(hipHostMalloc((void**)&st->hbuf, want, hipHostMallocDefault))) {
+    st->hbuf = nullptr;  // (the copy forms without a gather buffer)
     return nullptr;
   }
   st->hcap = want;
@@ -732,8 +737,8 @@ bool zc_ready(Staging* st, size_t bytes) {
     return false;
   if (st->zcap < bytes) {
     if (st->zh) {
-      (void)hipStreamSynchronize(st->stream);
-      (void)hipHostFree(st->zh);
+      hip_drop(hipStreamSynchronize(st->stream));
+      hip_drop(hipHostFree(st->zh));
       st->zh = st->zd = nullptr;
       st->zcap = 0;
     }
@@ -751,12 +756,12 @@ bool zc_ready(Staging* st, size_t bytes) {
   if (st->zcap < bytes) {
     const size_t want = std::max<size_t>(bytes + bytes / 4, kPoolMapped);
     void* d = nullptr;
-    if (hipHostMalloc((void**)&st->zh, want, hipHostMallocMapped) != hipSuccess) {
-      st->zh = nullptr;
+    if (!hip_drop(hipHostMalloc((void**)&st->zh, want, hipHostMallocMapped))) {
+      st->zh = nullptr;  // (the copy forms)
       return false;
     }
-    if (hipHostGetDevicePointer(&d, st->zh, 0) != hipSuccess) {
-      (void)hipHostFree(st->zh);
+    if (!hip_drop(hipHostGetDevicePointer(&d, st->zh, 0))) {
+      hip_drop(hipHostFree(st->zh));
       st->zh = nullptr;
       return false;
     }
@@ -780,17 +785,17 @@ bool ring_ready(Staging* st) {
   const size_t want = stage_chunk_bytes();
   if (st->ring && st->chunk == want) return true;
   if (st->ring) {
-    (void)hipStreamSynchronize(st->stream);
-    (void)hipHostFree(st->ring);
+    hip_drop(hipStreamSynchronize(st->stream));
+    hip_drop(hipHostFree(st->ring));
     st->ring = nullptr;
   }
-  if (hipHostMalloc((void**)&st->ring, want * kStageSlots, hipHostMallocDefault) != hipSuccess) {
-    st->ring = nullptr;
+  if (!hip_drop(hipHostMalloc((void**)&st->ring, want * kStageSlots, hipHostMallocDefault))) {
+    st->ring = nullptr;  // (pageable copies)
     return false;
   }
   for (int i = 0; i < kStageSlots; ++i) {
-    if (!st->ev[i] && hipEventCreateWithFlags(&st->ev[i], hipEventDisableTiming) != hipSuccess) {
-      (void)hipHostFree(st->ring);
+    if (!st->ev[i] && !hip_drop(hipEventCreateWithFlags(&st->ev[i], hipEventDisableTiming))) {
+      hip_drop(hipHostFree(st->ring));
       st->ring = nullptr;
       return false;
     }
@@ -924,7 +929,7 @@ int stage_d2h_sync_impl(Staging* st, const std::vector<D2HSeg>& segs) {
 // the thread's next call reuses its staging buffers).
 int stage_d2h_sync(Staging* st, const std::vector<D2HSeg>& segs) {
   const int rc = stage_d2h_sync_impl(st, segs);
-  if (rc != LEOEC_OK) (void)hipStreamSynchronize(st->stream);
+  if (rc != LEOEC_OK) hip_drop(hipStreamSynchronize(st->stream));
   return rc;
 }
 
@@ -962,8 +967,8 @@ int get_staging(Staging** out) {
 int dev_buf(Staging* st, size_t bytes) {
   if (st->cap >= bytes) return LEOEC_OK;
   if (st->buf) {
-    (void)hipStreamSynchronize(st->stream);
-    (void)hipFree(st->buf);
+    hip_drop(hipStreamSynchronize(st->stream));
+    hip_drop(hipFree(st->buf));
     st->buf = nullptr;
     st->cap = 0;
   }
@@ -1052,7 +1057,7 @@ int zc_chunked(const Plan& plan, Staging* st, const std::vector<ZcIn>& in,
       st->ev[nc] = nullptr;
       // chunks 0 .. nc-1 may still be reading and writing the mapped buffer
       // that this thread's next call repacks: drain them first
-      (void)hipStreamSynchronize(st->stream);
+      hip_drop(hipStreamSynchronize(st->stream));
       return LEOEC_E_HIP;
     }
     std::vector<Shard> si(nin), so(nout);
@@ -1066,7 +1071,7 @@ int zc_chunked(const Plan& plan, Staging* st, const std::vector<ZcIn>& in,
     int rc = run_plan(plan, si, so, len, 1, st->stream);
     if (rc == LEOEC_OK && hipEventRecord(st->ev[nc], st->stream) != hipSuccess) rc = LEOEC_E_HIP;
     if (rc) {
-      (void)hipStreamSynchronize(st->stream);
+      hip_drop(hipStreamSynchronize(st->stream));
       return rc;
     }
   }
@@ -1075,7 +1080,7 @@ int zc_chunked(const Plan& plan, Staging* st, const std::vector<ZcIn>& in,
   for (uint64_t c0 = 0; c0 < bs; c0 += cw, ++c) {
     const uint64_t len = std::min(cw, bs - c0);
     if (hipEventSynchronize(st->ev[c]) != hipSuccess) {
-      (void)hipStreamSynchronize(st->stream);
+      hip_drop(hipStreamSynchronize(st->stream));
       return LEOEC_E_HIP;
     }
     for (int o = 0; o < nout; ++o) {
@@ -1140,7 +1145,7 @@ int run_host_map(const Plan& plan, const uint8_t* const* blocks, const std::vect
   if (rc) {
     // copies already queued may still read this thread's pinned buffer:
     // drain them before the next call reuses it
-    (void)hipStreamSynchronize(st->stream);
+    hip_drop(hipStreamSynchronize(st->stream));
     st->zc = false;
     return rc;
   }
@@ -1252,7 +1257,7 @@ int op_encode(int coding, int k, int m, int w, const uint8_t* obj, uint64_t size
   else rc = stage_h2d_segs(st, st->buf, {H2DSeg{obj, 0, (size_t)size}});
   if (rc == LEOEC_OK) rc = run_plan(*plan, in, par, bs, 1, st->stream);
   if (rc) {
-    (void)hipStreamSynchronize(st->stream);  // queued copies may still read the caller's object
+    hip_drop(hipStreamSynchronize(st->stream));  // queued copies may still read the caller's object
     st->zc = false;
     return rc;
   }
@@ -1516,15 +1521,25 @@ int warm_device(int dev) {
   if (!known || dev < 0 || dev >= kMaxDevices) return LEOEC_OK;
   static std::once_flag once[kMaxDevices];
   std::call_once(once[dev], [dev] {
+    // Best effort: every HIP failure below is swallowed here, and dropped
+    // from the thread's last-error slot where it is swallowed (hip_drop; the
+    // failures of calls made further down are dropped by the clears below,
+    // each the warm-up's own)
     DeviceScope on(dev);
-    if (!on.ok()) return;
+    if (!on.ok()) {
+      (void)hipGetLastError();  // the scope's hipGetDevice / hipSetDevice
+      return;
+    }
     Staging* st;
-    if (get_staging(&st)) return;
+    if (get_staging(&st)) {
+      (void)hipGetLastError();  // get_staging's hipGetDevice / stream creation
+      return;
+    }
     constexpr size_t kScratch = 256u << 10, kPar = 128u << 10;
     uint8_t* d = nullptr;
-    if (hipMalloc(&d, kScratch) != hipSuccess) return;
+    if (!hip_drop(hipMalloc(&d, kScratch))) return;
     std::vector<uint8_t> h(kScratch, 0);
-    if (hipMemcpyAsync(d, h.data(), kScratch, hipMemcpyHostToDevice, st->stream) == hipSuccess) {
+    if (hip_drop(hipMemcpyAsync(d, h.data(), kScratch, hipMemcpyHostToDevice, st->stream))) {
       struct Warm {
         int coding, k, m, w;
       };
@@ -1534,31 +1549,34 @@ int warm_device(int dev) {
       for (int w : {3, 5, 7, 11, 13}) codes.push_back({LEOEC_LIBERATION, 2, 2, w});
       codes.push_back({LEOEC_VANDRS, 2, 1, 16});
       codes.push_back({LEOEC_VANDRS, 2, 1, 32});
+      bool launch_failed = false;
       for (const Warm& c : codes) {
-        (void)op_encode_dev(c.coding, c.k, c.m, c.w, d, kPar, 1024, 1, d + kPar, kPar, st->stream);
+        launch_failed |= op_encode_dev(c.coding, c.k, c.m, c.w, d, kPar, 1024, 1, d + kPar, kPar,
+                                       st->stream) != LEOEC_OK;
         if (c.coding == LEOEC_LIBERATION) {  // the syndrome kernels' code objects (lib_inst.hip)
           const int erased = 0;
-          (void)op_decode_dev(c.coding, c.k, c.m, c.w, d, kPar, 1024, 1, d + kPar, kPar, &erased,
-                              1, st->stream);
+          launch_failed |= op_decode_dev(c.coding, c.k, c.m, c.w, d, kPar, 1024, 1, d + kPar, kPar,
+                                         &erased, 1, st->stream) != LEOEC_OK;
         }
       }
-      (void)hipMemcpyAsync(h.data(), d + kPar, 4096, hipMemcpyDeviceToHost, st->stream);
+      if (launch_failed) (void)hipGetLastError();  // a warm-up launch's (or its table upload's)
+      hip_drop(hipMemcpyAsync(h.data(), d + kPar, 4096, hipMemcpyDeviceToHost, st->stream));
     }
-    (void)hipStreamSynchronize(st->stream);
-    (void)hipFree(d);
+    hip_drop(hipStreamSynchronize(st->stream));
+    hip_drop(hipFree(d));
     // the pools: streams and mapped buffers for the next calling threads
     ResourcePool& p = g_pool[dev];
     for (int i = 0; i < kPoolStreams; ++i) {
       hipStream_t s = nullptr;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
+      if (!hip_drop(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) break;
       uint8_t* h = nullptr;
       void* dp = nullptr;
-      if (hipHostMalloc((void**)&h, kPoolMapped, hipHostMallocMapped) == hipSuccess) {
-        if (hipHostGetDevicePointer(&dp, h, 0) == hipSuccess) {
+      if (hip_drop(hipHostMalloc((void**)&h, kPoolMapped, hipHostMallocMapped))) {
+        if (hip_drop(hipHostGetDevicePointer(&dp, h, 0))) {
           std::lock_guard<std::mutex> l(p.mu);
           p.mapped.push_back(ResourcePool::Mapped{h, static_cast<uint8_t*>(dp), kPoolMapped});
         } else {
-          (void)hipHostFree(h);
+          hip_drop(hipHostFree(h));
         }
       }
       std::lock_guard<std::mutex> l(p.mu);
@@ -1571,7 +1589,7 @@ int warm_device(int dev) {
 
 int warm_current_device() {
   int dev = -1;
-  if (device_init() != LEOEC_OK || hipGetDevice(&dev) != hipSuccess) return LEOEC_OK;
+  if (device_init() != LEOEC_OK || !hip_drop(hipGetDevice(&dev))) return LEOEC_OK;
   return warm_device(dev);
 }
 

@@ -70,6 +70,25 @@ int device_init();
 const std::vector<int>& host_devices();
 constexpr int kMaxDevices = 64;
 
+// For a HIP call whose failure the engine recovers from or has nothing to do
+// about (a buffer that cannot be had: the call takes another form; a free or
+// a drain on a path that goes on): true when it succeeded.  A failure is
+// also taken out of the calling thread's last-error slot, where the runtime
+// left it and where the caller, or torch after its next launch, would find
+// an error that is nobody's any more (include/leoec.h, Conventions).  What
+// the clear drops is this call's own failure; an older error of the caller's
+// pending in the slot goes with it, which only host-memory calls can cause:
+// the *_dev entry points swallow no failure, with two exceptions on paths
+// where a HIP call of their own has failed, which the contract leaves open —
+// the process's first call of any kind runs device_init, which passes over a
+// device whose property query fails, and heal's table upload frees its
+// buffer when the copy into it fails (that call returns LEOEC_E_HIP).
+inline bool hip_drop(hipError_t e) {
+  if (e == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
 // Makes `dev` the calling thread's current HIP device for a scope and puts
 // the previous one back (host-memory calls run on the device the dispatcher
 // picked without changing the caller's own device).

@@ -41,9 +41,8 @@ int launch_gfb_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint6
   // kObjMapMaxTiles tiles; Knobs::gfbit_xmap = 0 turns it off (A/B)
   a.xmap = (XMAP == 0 && a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
   if (KR > 0 && nk > KR) return LEOEC_E_ARG;
-  hipLaunchKernelGGL((gfbit_apply<W, R, LW, ACC, PF, CEIL, KR, WG, XMAP, WAVES>),
-                     dim3((uint32_t)(no * a.tiles)), dim3(WG), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfbit_apply<W, R, LW, ACC, PF, CEIL, KR, WG, XMAP, WAVES>),
+                       dim3((uint32_t)(no * a.tiles)), dim3(WG), 0, s, a);
 }
 
 constexpr int kPF = 1;  // gfbit_apply: blocks of load look-ahead
@@ -189,9 +188,8 @@ int launch_gfbk_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint
       a.coef[i][j] = j < nk ? p.coef[(size_t)(r0 + i) * p.K + j0 + j] : 0u;
   }
   a.xmap = (a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
-  hipLaunchKernelGGL((gfbk_apply<10, LA, WG, MASK, WAVES>), dim3((uint32_t)(no * a.tiles)),
-                     dim3(WG), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfbk_apply<10, LA, WG, MASK, WAVES>), dim3((uint32_t)(no * a.tiles)),
+                       dim3(WG), 0, s, a);
 }
 
 // The shipped gfbk form: 64 lanes, 3 blocks of loads in flight, one wave per
@@ -372,9 +370,8 @@ int launch_gfb2_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint
   }
   for (int i = 0; i < R; ++i) a.out[i] = dev_shard(p.out[r0 + i], o0);
   a.xmap = (a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
-  hipLaunchKernelGGL((gfb2_apply<W, R, LW, ACC, PF, WG>), dim3((uint32_t)(no * a.tiles)),
-                     dim3(WG), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfb2_apply<W, R, LW, ACC, PF, WG>), dim3((uint32_t)(no * a.tiles)),
+                       dim3(WG), 0, s, a);
 }
 
 constexpr int kPF2 = 0;  // gfb2_apply: load-then-compute (LEOEC_GFBIT_PF=1: prefetching loop)

@@ -120,9 +120,8 @@ int launch_gfbx_8(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint
       a.coef[i][j] = j < nk ? p.coef[(size_t)(r0 + i) * p.K + j0 + j] : 0u;
   }
   a.xmap = (a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
-  hipLaunchKernelGGL((gfbx_apply<8>), dim3((uint32_t)(no * a.tiles)), dim3(2 * kGfbxLanes), 0, s,
-                     a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfbx_apply<8>), dim3((uint32_t)(no * a.tiles)), dim3(2 * kGfbxLanes), 0, s,
+                       a);
 }
 
 // gfba_apply (measurement form, LEOEC_GFBIT_FORM=3; no accumulation, <= 16
@@ -258,9 +257,8 @@ int launch_gfba_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, uint
       a.coef[i][j] = j < nk ? p.coef[(size_t)(r0 + i) * p.K + j0 + j] : 0u;
   }
   a.xmap = (a.tiles <= kObjMapMaxTiles && knobs().gfbit_xmap != 0) ? 1u : 0u;
-  hipLaunchKernelGGL((gfba_apply<8, R, WG, CEIL, NB>), dim3((uint32_t)(no * a.tiles)), dim3(WG),
-                     0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfba_apply<8, R, WG, CEIL, NB>), dim3((uint32_t)(no * a.tiles)), dim3(WG),
+                       0, s, a);
 }
 
 template <int WG, bool CEIL, int NB>
@@ -303,9 +301,8 @@ int launch_gfb_lds_t(const GfBitApply& p, int r0, int j0, int nk, uint64_t o0, u
     for (int j = 0; j < kMaxK; ++j)
       a.coef[i][j] = j < nk ? p.coef[(size_t)(r0 + i) * p.K + j0 + j] : 0u;
   }
-  hipLaunchKernelGGL((gfbit_lds_apply<W, R, ACC>), dim3((uint32_t)(no * a.tiles)),
-                     dim3(kGfbLdsThreads), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfbit_lds_apply<W, R, ACC>), dim3((uint32_t)(no * a.tiles)),
+                       dim3(kGfbLdsThreads), 0, s, a);
 }
 
 // Measurement forms of the w = 8 kernel (Knobs::gfbit_*): lane width

@@ -233,8 +233,8 @@ int launch_gfs_t(const GfApply& p, const Chunk& c, hipStream_t s) {
   a.xmap = a.tiles <= kObjMapMaxTiles ? 1u : 0u;
   const uint64_t grid = c.no * a.tiles;
   if (grid == 0 || grid > 0x7FFFFFFFull) return LEOEC_E_ARG;
-  hipLaunchKernelGGL((gfs_apply<W, R, ACC, MODE, PF>), dim3((uint32_t)grid), dim3(kGfsLanes), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfs_apply<W, R, ACC, MODE, PF>), dim3((uint32_t)grid), dim3(kGfsLanes), 0,
+                       s, a);
 }
 
 template <int W>

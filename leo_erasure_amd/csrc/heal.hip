@@ -80,7 +80,7 @@ int heal_table(const Code& c, const uint32_t** out) {
   if (hipMalloc(&t->dev, bytes) != hipSuccess) return LEOEC_E_NOMEM;
   // a blocking copy: the image is on the device before any launch reads it
   if (hipMemcpy(t->dev, t->host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(t->dev);
+    hip_drop(hipFree(t->dev));
     return LEOEC_E_HIP;
   }
   *out = t->dev;

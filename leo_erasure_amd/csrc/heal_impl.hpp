@@ -182,8 +182,8 @@ int launch_gf8_heal_t(HealArgs a, hipStream_t s) {
   const Gf8Grid g = gf8_grid_env(a.bs);
   const uint32_t wg = g.wg;
   gf8_set_grid(a, g, a.nobj);
-  hipLaunchKernelGGL((gf8_heal<K, kMaxR, kGf8HealWaves>), dim3(a.nobj * a.tiles), dim3(wg), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gf8_heal<K, kMaxR, kGf8HealWaves>), dim3(a.nobj * a.tiles), dim3(wg), 0, s,
+                       a);
 }
 
 using HealFn = int (*)(HealArgs, hipStream_t);

@@ -142,7 +142,11 @@ struct Queue {
 
 // Wait for `ev` without holding the queue lock: (Knobs::hostq_sync = 1) a
 // hipEventQuery poll with yields, else hipEventSynchronize (= 2: on an event
-// created hipEventBlockingSync, which sleeps instead of spinning).
+// created hipEventBlockingSync, which sleeps instead of spinning).  Only the
+// queue's own worker and completer threads wait here: whether the runtime
+// keeps a poll's hipErrorNotReady in the polling thread's last-error slot is
+// not known, and does not matter, since no launch status is read from a slot
+// (kernels.hpp launch_kernel) and no caller's code runs on these threads.
 hipError_t wait_event(hipEvent_t ev) {
   if (knobs().hostq_sync == 1) {
     for (;;) {
@@ -160,7 +164,7 @@ hipError_t wait_event(hipEvent_t ev) {
 // copy is done.
 bool wait_h2d_or_closed(hipEvent_t ev, const Queue* q) {
   if (knobs().hostq_sync != 1) {
-    (void)wait_event(ev);  // (a failed copy is the batch's status: the completer reports it)
+    hip_drop(wait_event(ev));  // (a failed copy is the batch's status: the completer reports it)
     return true;
   }
   for (;;) {
@@ -196,19 +200,19 @@ int slot_alloc(Slot* s) {
       hipEventCreateWithFlags(&s->ev_k, hipEventDisableTiming) != hipSuccess ||
       !group_events(s)) {
     for (hipEvent_t* e : {&s->ev, &s->ev_blk, &s->ev_h2d, &s->ev_k}) {
-      if (*e) (void)hipEventDestroy(*e);
+      if (*e) hip_drop(hipEventDestroy(*e));
       *e = nullptr;
     }
     for (int g = 0; g < kMaxGroups - 1; ++g) {
-      if (s->ev_grp[g]) (void)hipEventDestroy(s->ev_grp[g]);
-      if (s->ev_grp_blk[g]) (void)hipEventDestroy(s->ev_grp_blk[g]);
+      if (s->ev_grp[g]) hip_drop(hipEventDestroy(s->ev_grp[g]));
+      if (s->ev_grp_blk[g]) hip_drop(hipEventDestroy(s->ev_grp_blk[g]));
       s->ev_grp[g] = s->ev_grp_blk[g] = nullptr;
     }
-    if (s->h_in) (void)hipHostFree(s->h_in);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->d_in) (void)hipFree(s->d_in);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->h_in) hip_drop(hipHostFree(s->h_in));
+    if (s->h_out) hip_drop(hipHostFree(s->h_out));
+    if (s->d_in) hip_drop(hipFree(s->d_in));
+    if (s->d_out) hip_drop(hipFree(s->d_out));
+    if (s->stream) hip_drop(hipStreamDestroy(s->stream));
     s->h_in = s->h_out = s->d_in = s->d_out = nullptr;
     s->stream = nullptr;
     return LEOEC_E_NOMEM;
@@ -355,21 +359,21 @@ int launch_slot(Slot* s) {
     // a failure part-way: drain whatever this batch enqueued on the three
     // streams (every group copy that was issued), so the event below (on the
     // slot's stream) follows all of it
-    (void)hipStreamSynchronize(cin);
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipStreamSynchronize(cout);
+    hip_drop(hipStreamSynchronize(cin));
+    hip_drop(hipStreamSynchronize(s->stream));
+    hip_drop(hipStreamSynchronize(cout));
     last = s->stream;
   }
   if (hipEventRecord(s->ev_done, last) != hipSuccess) {
-    (void)hipStreamSynchronize(last);  // no event to wait on: drain here
-    if (split) (void)hipStreamSynchronize(s->stream);
+    hip_drop(hipStreamSynchronize(last));  // no event to wait on: drain here
+    if (split) hip_drop(hipStreamSynchronize(s->stream));
     s->grp_rc[G - 1] = LEOEC_E_HIP;
   }
   return rc;
 }
 
 void worker_main(Queue* q) {
-  (void)hipSetDevice(q->device);
+  hip_drop(hipSetDevice(q->device));
   std::unique_lock<std::mutex> lk(q->mu);
   for (;;) {
     const int depth = knobs().hostq_depth;
@@ -432,7 +436,7 @@ void worker_main(Queue* q) {
 }
 
 void completer_main(Queue* q) {
-  (void)hipSetDevice(q->device);
+  hip_drop(hipSetDevice(q->device));
   std::unique_lock<std::mutex> lk(q->mu);
   for (;;) {
     q->cv_complete.wait(lk, [q] { return !q->inflight.empty(); });
@@ -590,6 +594,10 @@ Queue* queue_for(int lane) {
     if (Queue* q = build_queue(lane)) {
       L.q.store(q, std::memory_order_release);
       g_queues_built.fetch_add(1, std::memory_order_relaxed);
+    } else {
+      // the lane goes without batching (per-thread path): drops the failure
+      // of build_queue's HIP call that made it so, which is no call's error
+      (void)hipGetLastError();
     }
   });
   return L.q.load(std::memory_order_acquire);

@@ -221,8 +221,8 @@ int launch_lib(const BitApply& p, LibFn fn, uint32_t lanes, hipStream_t s) {
       if (a.out[r].valid < vmin) vmin = a.out[r].valid;
     }
     a.vmin = vmin;
-    hipLaunchKernelGGL(fn, dim3((uint32_t)(no * tiles)), dim3(lanes), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(fn, dim3((uint32_t)(no * tiles)), dim3(lanes), 0, s, a) != LEOEC_OK)
+      return LEOEC_E_HIP;
   }
   return LEOEC_OK;
 }
@@ -399,8 +399,8 @@ int launch(const LibDecApply& p, hipStream_t s) {
         a.mbits[b][q] = (b < nout && q < 2 * w) ? p.mbits[(size_t)b * 2 * w + q] : 0u;
     }
     a.vmin = vmin;
-    hipLaunchKernelGGL(fn, dim3((uint32_t)(no * tiles)), dim3(lanes), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(fn, dim3((uint32_t)(no * tiles)), dim3(lanes), 0, s, a) != LEOEC_OK)
+      return LEOEC_E_HIP;
   }
   return LEOEC_OK;
 }
@@ -467,8 +467,7 @@ int launch(const BitApply& p, hipStream_t s) {
         const int ro = RP <= 8 ? 8 : RP <= 16 ? 16 : 32;
         if (form != 4) fn = bit_kernel(ro, acc, form == 8 ? 4 : form);
 #endif
-        hipLaunchKernelGGL(fn, grid, block, 0, s, a);
-        if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+        if (launch_kernel(fn, grid, block, 0, s, a) != LEOEC_OK) return LEOEC_E_HIP;
       }
     }
   }

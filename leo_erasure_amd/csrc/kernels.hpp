@@ -20,6 +20,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/leoec.h"
+
 namespace leoec {
 
 struct Shard {
@@ -72,6 +74,31 @@ struct LibDecApply {
   uint64_t block_size = 0;
   uint64_t nobj = 0;
 };
+
+// The one way a kernel is launched, product and measurement forms alike: the
+// status is the one hipLaunchKernel returns for THIS launch.  The thread's
+// sticky last-error slot (hipGetLastError / hipPeekAtLastError) is neither
+// read nor cleared: it holds the last failure of any HIP call on the thread —
+// the caller's own, or one the engine recovered from — which says nothing
+// about this launch (include/leoec.h, Conventions).  Arguments are converted
+// to the kernel's parameter types.  For the translation units that hold
+// kernels: the host C++ (engine.cpp, hostq.cpp) launches nothing, and builds
+// against any HIP header, one without launch types included.
+#ifdef __HIPCC__
+template <class T>
+struct launch_arg {
+  using type = T;
+};
+template <class... P>
+inline int launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                         const typename launch_arg<P>::type&... args) {
+  void* argv[sizeof...(P) + 1] = {const_cast<void*>(static_cast<const void*>(&args))..., nullptr};
+  return hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, lds, s) ==
+                 hipSuccess
+             ? LEOEC_OK
+             : LEOEC_E_HIP;
+}
+#endif  // __HIPCC__
 
 // Enqueue on `stream`; returns a leoec_status.
 int launch(const GfApply& plan, hipStream_t stream);

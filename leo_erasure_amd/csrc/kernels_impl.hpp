@@ -1451,17 +1451,14 @@ int launch_gf8_t(const GfApply& p, const Chunk& c, hipStream_t s) {
     for (int j = 0; ones && j < K; ++j)
       if ((r == 0 || j == 0) && (p.coef[(size_t)r * p.K + j] & 0xFFu) != 1u) ones = false;
   if (ONES && ones) {
-    hipLaunchKernelGGL((gf8_apply<K, R, ACC, CPT, NT, false, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, true, EARLY>),
-                       dim3(grid), dim3(wg), 0, s, a);
-    return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+    return launch_kernel((gf8_apply<K, R, ACC, CPT, NT, false, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, true, EARLY>),
+                         dim3(grid), dim3(wg), 0, s, a);
   }
   if (branchy)
-    hipLaunchKernelGGL((gf8_apply<K, R, ACC, CPT, NT, true, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, false, EARLY>),
+    return launch_kernel((gf8_apply<K, R, ACC, CPT, NT, true, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, false, EARLY>),
+                         dim3(grid), dim3(wg), 0, s, a);
+  return launch_kernel((gf8_apply<K, R, ACC, CPT, NT, false, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, false, EARLY>),
                        dim3(grid), dim3(wg), 0, s, a);
-  else
-    hipLaunchKernelGGL((gf8_apply<K, R, ACC, CPT, NT, false, COPY, PIPE, LDS, WAVES, WG, XMAP, BUF, false, EARLY>),
-                       dim3(grid), dim3(wg), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
 }
 
 using ChunkFn = int (*)(const GfApply&, const Chunk&, hipStream_t);

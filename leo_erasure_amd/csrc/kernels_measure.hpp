@@ -477,9 +477,8 @@ int launch_gfw_t(const GfApply& p, const Chunk& c, hipStream_t s) {
   }
   a.tiles = c.tiles;
   a.vmin = vmin;
-  hipLaunchKernelGGL((gfw_apply<W, R, ACC>), dim3((uint32_t)(c.no * c.tiles)), dim3(kThreads), 0,
-                     s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfw_apply<W, R, ACC>), dim3((uint32_t)(c.no * c.tiles)), dim3(kThreads), 0,
+                       s, a);
 }
 
 template <int R, bool ACC>
@@ -499,9 +498,8 @@ int launch_gf16_t(const GfApply& p, const Chunk& c, hipStream_t s) {
   }
   a.tiles = c.tiles;
   a.vmin = vmin;
-  hipLaunchKernelGGL((gf16_apply<R, ACC>), dim3((uint32_t)(c.no * c.tiles)), dim3(kThreads), 0, s,
-                     a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gf16_apply<R, ACC>), dim3((uint32_t)(c.no * c.tiles)), dim3(kThreads), 0, s,
+                       a);
 }
 
 template <int W, int R, bool ACC, int CPT>
@@ -527,8 +525,7 @@ int launch_gfp_t(const GfApply& p, const Chunk& c, hipStream_t s) {
   const uint32_t cap = (uint32_t)device_cus() * gfp_blocks_per_cu();
   const uint32_t per = (a.total_tiles + cap - 1) / cap;
   const uint32_t grid = (a.total_tiles + per - 1) / per;
-  hipLaunchKernelGGL((gfp_apply<W, R, ACC, CPT>), dim3(grid), dim3(kThreads), 0, s, a);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gfp_apply<W, R, ACC, CPT>), dim3(grid), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace detail

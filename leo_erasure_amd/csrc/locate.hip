@@ -121,9 +121,9 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
       continue;
     }
     // no <= 2^31 - 1 words: one grid
-    hipLaunchKernelGGL(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, s, lost + o0, (uint32_t)no);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
+      return LEOEC_E_HIP;
   }
   return LEOEC_OK;
 }
@@ -324,12 +324,12 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
     if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
     if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
     a.parity = parity + o0 * parity_stride;
-    hipLaunchKernelGGL(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s, a,
-                       lost + o0);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
-    hipLaunchKernelGGL(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, s, lost + o0, (uint32_t)no);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s, a,
+                      lost + o0) != LEOEC_OK)
+      return LEOEC_E_HIP;
+    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
+      return LEOEC_E_HIP;
   }
   return LEOEC_OK;
 }

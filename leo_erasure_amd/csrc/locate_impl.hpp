@@ -133,9 +133,8 @@ int launch_gf8_locate_t(const GfApply& p, const uint32_t* ratio, uint64_t o0, ui
   const uint32_t wg = g.wg;
   gf8_set_grid(a, g, no);
   a.total_tiles = (uint32_t)(no * a.tiles);
-  hipLaunchKernelGGL((gf8_locate<K, R, kGf8CheckWaves>), dim3(a.total_tiles), dim3(wg), 0, s, a, t,
-                     lost + o0);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gf8_locate<K, R, kGf8CheckWaves>), dim3(a.total_tiles), dim3(wg), 0, s, a,
+                       t, lost + o0);
 }
 
 using LocateFn = int (*)(const GfApply&, const uint32_t*, uint64_t, uint64_t, uint32_t*,

@@ -149,10 +149,10 @@ struct ScrubSteps final : LocateSteps {
     uint32_t* const words = report + o0;
     if (table && hipMemsetAsync(header(), 0, kScrubHeader, s) != hipSuccess) return LEOEC_E_HIP;
     // no <= 2^31 - 1 words: one grid
-    hipLaunchKernelGGL(scrub_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, s, words, (uint32_t)no, table ? list() : nullptr, header(),
-                       totals);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(scrub_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                      dim3(kThreads), 0, s, words, (uint32_t)no, table ? list() : nullptr, header(),
+                      totals) != LEOEC_OK)
+      return LEOEC_E_HIP;
     if (!table) return LEOEC_OK;
     HealArgs a;
     a.objs = objs + o0 * obj_stride;

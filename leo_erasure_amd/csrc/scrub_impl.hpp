@@ -150,9 +150,8 @@ int launch_gf8_heal_list_t(HealArgs a, const uint32_t* list, const uint32_t* cou
   uint64_t grid = (uint64_t)device_cus() * gf8_heal_list_resident(wg);
   grid = grid < all ? grid : all;
   if (cap != 0u && grid > cap) grid = cap;
-  hipLaunchKernelGGL((gf8_heal_list<K, kMaxR, kGf8HealWaves>), dim3((uint32_t)grid), dim3(wg), 0, s,
-                     a, list, count);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gf8_heal_list<K, kMaxR, kGf8HealWaves>), dim3((uint32_t)grid), dim3(wg), 0,
+                       s, a, list, count);
 }
 
 using HealListFn = int (*)(HealArgs, const uint32_t*, const uint32_t*, uint32_t, hipStream_t);

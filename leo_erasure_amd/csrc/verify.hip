@@ -139,10 +139,10 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     std::vector<Shard> cin(in);
     for (Shard& sh : cin) sh.base += o0 * obj_stride;
     if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
-    hipLaunchKernelGGL(verify_compare, dim3((uint32_t)(no * m * tiles)), dim3(kThreads), 0, s, ws,
-                       parity + o0 * parity_stride, parity_stride, (uint32_t)bs, (uint32_t)m, tiles,
-                       flags + o0);
-    if (hipGetLastError() != hipSuccess) return LEOEC_E_HIP;
+    if (launch_kernel(verify_compare, dim3((uint32_t)(no * m * tiles)), dim3(kThreads), 0, s, ws,
+                      parity + o0 * parity_stride, parity_stride, (uint32_t)bs, (uint32_t)m, tiles,
+                      flags + o0) != LEOEC_OK)
+      return LEOEC_E_HIP;
   }
   return LEOEC_OK;
 }

@@ -91,15 +91,13 @@ int launch_gf8_check_t(const GfApply& p, uint64_t o0, uint64_t no, uint32_t* fla
 #ifdef LEOEC_MEASURE
   if constexpr (K == 10 && R == 4) {
     if (verify_form_env() == 2) {
-      hipLaunchKernelGGL((gf8_check<K, R, kGf8Default.waves>), dim3(a.total_tiles), dim3(wg), 0, s,
-                         a, flags + o0);
-      return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+      return launch_kernel((gf8_check<K, R, kGf8Default.waves>), dim3(a.total_tiles), dim3(wg), 0,
+                           s, a, flags + o0);
     }
   }
 #endif
-  hipLaunchKernelGGL((gf8_check<K, R, kGf8CheckWaves>), dim3(a.total_tiles), dim3(wg), 0, s, a,
-                     flags + o0);
-  return hipGetLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  return launch_kernel((gf8_check<K, R, kGf8CheckWaves>), dim3(a.total_tiles), dim3(wg), 0, s, a,
+                       flags + o0);
 }
 
 using CheckFn = int (*)(const GfApply&, uint64_t, uint64_t, uint32_t*, hipStream_t);

@@ -20,6 +20,8 @@
 
 #include <cstdint>
 
+#include "kernels.hpp"  // launch_kernel
+
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -123,8 +125,8 @@ extern "C" __attribute__((visibility("default"))) int leoec_measure_xor_pattern_
   XorArgs a;
   uint32_t grid;
   if (!xor_args(objs, stride, size, nobj, parity, pstride, &a, &grid)) return -1;
-  hipLaunchKernelGGL(xor_pattern, dim3(grid), dim3(kLanes), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  const int rc = leoec::launch_kernel(xor_pattern, dim3(grid), dim3(kLanes), 0, stream, a);
+  return rc == LEOEC_OK ? 0 : -2;
 }
 
 // half = 0: the reads of xor_pattern alone (parity untouched); 1: its writes
@@ -137,9 +139,9 @@ extern "C" __attribute__((visibility("default"))) int leoec_measure_stream_half_
   uint32_t grid;
   if ((half != 0 && half != 1) || !xor_args(objs, stride, size, nobj, parity, pstride, &a, &grid))
     return -1;
-  if (half == 0)
-    hipLaunchKernelGGL(stream_half<true>, dim3(grid), dim3(kLanes), 0, stream, a, 0x9E3779B9u);
-  else
-    hipLaunchKernelGGL(stream_half<false>, dim3(grid), dim3(kLanes), 0, stream, a, 0u);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  const dim3 g(grid), b(kLanes);
+  const int rc = half == 0
+                     ? leoec::launch_kernel(stream_half<true>, g, b, 0, stream, a, 0x9E3779B9u)
+                     : leoec::launch_kernel(stream_half<false>, g, b, 0, stream, a, 0u);
+  return rc == LEOEC_OK ? 0 : -2;
 }

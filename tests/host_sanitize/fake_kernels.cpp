@@ -24,9 +24,19 @@ inline void wr(const Shard& s, uint64_t o, uint64_t pos, uint8_t v) {
   if (pos < s.valid) const_cast<uint8_t*>(s.base)[o * s.stride + pos] = v;
 }
 
+// The four launch() overloads stand for the product launchers, and they judge
+// their status the strictest way a launcher could: as one that reads the
+// calling thread's sticky last-error slot (hip/hip_runtime.h) after its
+// launch.  The work is queued either way, as a real launch is; the status is
+// LEOEC_E_HIP when the slot was not clean on entry, and the slot is left as it
+// was.  The product launchers take the status hipLaunchKernel returns and
+// never look at the slot, so they are immune to this; the harness is not, on
+// purpose: an engine fallback that swallows a HIP failure and leaves it in
+// the slot (zc_ready, gather_buf, ring_ready, reclaim_drain) makes the
+// thread's next launch fail here, whatever form the product launchers take.
 int enqueue(hipStream_t s, std::function<void()> f) {
   fake_stream(s)->push(std::move(f));
-  return LEOEC_OK;
+  return hipPeekAtLastError() == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
 }
 
 // bit i of c * 2^x in GF(2^w): the (i, x) entry of "multiply by c"

@@ -17,7 +17,14 @@
 //     hipHostMalloc (pageable) complete before hipMemcpyAsync returns, as
 //     the HIP runtime's staged pageable copies do, pinned copies are
 //     asynchronous;
-//   * two "gfx950" devices with a per-thread current device.
+//   * two "gfx950" devices with a per-thread current device;
+//   * the per-thread last-error slot, with the sticky semantics HIP documents
+//     (the CUDA-compatible ones): every entry point that returns a status
+//     other than hipSuccess or hipErrorNotReady stores it in the calling
+//     thread's slot, success never overwrites it, hipGetLastError returns and
+//     clears it, hipPeekAtLastError returns it.  Whether the installed
+//     runtime also stores hipErrorNotReady, or lets a later successful call
+//     overwrite the slot, is NOT known here: the engine may rely on neither.
 // Kernels are the engine's launch() entry points, implemented on the CPU in
 // fake_kernels.cpp and run on the stream's thread.
 #pragma once
@@ -184,6 +191,48 @@ inline int& fail_event_create_in() {
   return n;
 }
 inline void fail_nth_event_create(int n) { fail_event_create_in() = n; }
+// ... and the n-th hipHostMalloc / hipHostGetDevicePointer of the calling
+// thread (hipErrorOutOfMemory / hipErrorInvalidValue): the pinned-memory
+// pressure under which the engine's staging falls back to its copy forms
+// (engine.cpp zc_ready, gather_buf, ring_ready).
+// `count` calls in a row fail, the n-th being the first (a zero-copy buffer
+// and the gather buffer behind it are two consecutive hipHostMallocs).
+inline int& fail_host_malloc_in() {
+  static thread_local int n = 0;
+  return n;
+}
+inline int& fail_host_malloc_count() {
+  static thread_local int n = 0;
+  return n;
+}
+inline void fail_nth_host_malloc(int n, int count = 1) {
+  fail_host_malloc_in() = n;
+  fail_host_malloc_count() = n > 0 ? count : 0;
+}
+inline int& fail_host_get_device_pointer_in() {
+  static thread_local int n = 0;
+  return n;
+}
+inline void fail_nth_host_get_device_pointer(int n) { fail_host_get_device_pointer_in() = n; }
+// How many hipHostMalloc calls the calling thread has made, failed ones
+// included: a test that injects failures reads it before and after, to see
+// that the calls that failed were the only ones made, the ones it means.
+inline long& host_malloc_calls() {
+  static thread_local long n = 0;
+  return n;
+}
+
+// The calling thread's last-error slot (see the header comment).
+inline hipError_t& last_error() {
+  static thread_local hipError_t e = hipSuccess;
+  return e;
+}
+// What every fake entry point returns through: a failure is stored, success
+// and not-ready leave the slot as it is.
+inline hipError_t ret(hipError_t e) {
+  if (e != hipSuccess && e != hipErrorNotReady) last_error() = e;
+  return e;
+}
 
 // Thread teardown: set on a thread once the first of its thread_local
 // destructors has started (tls_teardown.cpp re-registers the marker after
@@ -219,7 +268,7 @@ inline hipError_t hipGetDeviceCount(int* n) {
 }
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int dev) {
   fakehip::live("hipGetDeviceProperties");
-  if (dev < 0 || dev >= fakehip::kDevices) return hipErrorInvalidDevice;
+  if (dev < 0 || dev >= fakehip::kDevices) return fakehip::ret(hipErrorInvalidDevice);
   std::memset(p, 0, sizeof(*p));
   std::strcpy(p->name, "fake MI355X (host sanitizer harness)");
   std::strcpy(p->gcnArchName, "gfx950:sramecc+:xnack-");
@@ -227,7 +276,7 @@ inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int dev) {
 }
 inline hipError_t hipSetDevice(int dev) {
   fakehip::live("hipSetDevice");
-  if (dev < 0 || dev >= fakehip::kDevices) return hipErrorInvalidDevice;
+  if (dev < 0 || dev >= fakehip::kDevices) return fakehip::ret(hipErrorInvalidDevice);
   fakehip::current_device() = dev;
   return hipSuccess;
 }
@@ -240,7 +289,7 @@ inline hipError_t hipGetDevice(int* dev) {
 inline hipError_t hipMalloc(void** p, size_t n) {
   fakehip::live("hipMalloc");
   *p = std::malloc(n ? n : 1);
-  if (!*p) return hipErrorOutOfMemory;
+  if (!*p) return fakehip::ret(hipErrorOutOfMemory);
   ++fakehip::live_allocs();
   return hipSuccess;
 }
@@ -257,8 +306,15 @@ inline hipError_t hipFree(void* p) {
 }
 inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) {
   fakehip::live("hipHostMalloc");
+  ++fakehip::host_malloc_calls();
+  int& inject = fakehip::fail_host_malloc_in();
+  if (inject > 0 && --inject == 0) {
+    if (--fakehip::fail_host_malloc_count() > 0) inject = 1;  // the next one fails too
+    *p = nullptr;
+    return fakehip::ret(hipErrorOutOfMemory);
+  }
   *p = std::malloc(n ? n : 1);
-  if (!*p) return hipErrorOutOfMemory;
+  if (!*p) return fakehip::ret(hipErrorOutOfMemory);
   ++fakehip::live_allocs();
   std::lock_guard<std::mutex> l(fakehip::pinned().mu);
   fakehip::pinned().blocks[(uintptr_t)*p] = n;
@@ -276,10 +332,15 @@ inline hipError_t hipHostFree(void* p) {
 }
 inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) {
   fakehip::live("hipHostGetDevicePointer");
+  int& inject = fakehip::fail_host_get_device_pointer_in();
+  if (inject > 0 && --inject == 0) {
+    *d = nullptr;
+    return fakehip::ret(hipErrorInvalidValue);
+  }
   // only pinned memory (hipHostMalloc, hipHostRegister) has a device address
   if (!fakehip::pinned().contains(h, 1)) {
     *d = nullptr;
-    return hipErrorInvalidValue;
+    return fakehip::ret(hipErrorInvalidValue);
   }
   *d = h;
   return hipSuccess;
@@ -306,7 +367,7 @@ inline hipError_t hipStreamSynchronize(hipStream_t s) {
 inline hipError_t hipStreamQuery(hipStream_t s) {
   fakehip::live("hipStreamQuery");
   fakehip::Stream* st = fake_stream(s);
-  return st->reached(st->ticket()) ? hipSuccess : hipErrorNotReady;
+  return st->reached(st->ticket()) ? hipSuccess : hipErrorNotReady;  // (not stored)
 }
 
 inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind kind,
@@ -338,7 +399,7 @@ inline hipError_t hipHostRegister(void* p, size_t n, unsigned) {
     --it;
     if (it->first + it->second > a) {
       ++pn.n_refused;
-      return hipErrorHostMemoryAlreadyRegistered;
+      return fakehip::ret(hipErrorHostMemoryAlreadyRegistered);
     }
   }
   ++pn.n_registered;
@@ -351,7 +412,7 @@ inline hipError_t hipHostUnregister(void* p) {
   fakehip::Pinned& pn = fakehip::pinned();
   std::lock_guard<std::mutex> l(pn.mu);
   auto it = pn.registered.find((uintptr_t)p);
-  if (it == pn.registered.end()) return hipErrorHostMemoryNotRegistered;
+  if (it == pn.registered.end()) return fakehip::ret(hipErrorHostMemoryNotRegistered);
   if (it->second != 0) {
     std::fprintf(stderr, "fake hip: hipHostUnregister(%p) with %d copies in flight\n", p,
                  it->second);
@@ -367,7 +428,7 @@ inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
   int& n = fakehip::fail_event_create_in();
   if (n > 0 && --n == 0) {
     *e = nullptr;
-    return hipErrorOutOfMemory;
+    return fakehip::ret(hipErrorOutOfMemory);
   }
   *e = new fakehip::Event;
   return hipSuccess;
@@ -394,7 +455,7 @@ inline hipError_t hipEventQuery(hipEvent_t e) {
     st = e->s;
     t = e->t;
   }
-  return !st || st->reached(t) ? hipSuccess : hipErrorNotReady;
+  return !st || st->reached(t) ? hipSuccess : hipErrorNotReady;  // (not stored)
 }
 inline hipError_t hipEventSynchronize(hipEvent_t e) {
   fakehip::live("hipEventSynchronize");
@@ -428,5 +489,11 @@ inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
 inline const char* hipGetErrorString(hipError_t) { return "fake hip error"; }
 inline hipError_t hipGetLastError() {
   fakehip::live("hipGetLastError");
-  return hipSuccess;
+  const hipError_t e = fakehip::last_error();
+  fakehip::last_error() = hipSuccess;
+  return e;
+}
+inline hipError_t hipPeekAtLastError() {
+  fakehip::live("hipPeekAtLastError");
+  return fakehip::last_error();
 }

@@ -77,38 +77,63 @@ void prepare(Case* c, uint32_t seed) {
 
 const uint8_t* block(const Case& c, int id) { return c.ref.data() + (size_t)id * c.bs; }
 
+// include/leoec.h, Conventions: a call that returned LEOEC_OK on a thread whose
+// HIP last-error slot was clean leaves it clean (the engine drops the HIP
+// failures it recovers from).  Every phase's threads start clean and check
+// after every call; a leftover is reported once and cleared.
+void slot_clean(const char* op, const Case& c) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    fail(std::string(op) + " " + name(c) + " left HIP error " + std::to_string((int)e) +
+         " in the thread's last-error slot");
+}
+
+int encode_case(const Case& c) {
+  const int n = c.k + c.m;
+  std::vector<uint8_t> out((size_t)(n - c.filled) * c.bs + 1);
+  const int rc =
+      leoec_encode(c.coding, c.k, c.m, c.w, c.data.data(), c.size, out.data(), out.size());
+  if (rc || std::memcmp(out.data(), block(c, c.filled), (size_t)(n - c.filled) * c.bs))
+    fail("encode " + name(c) + " rc " + std::to_string(rc));
+  slot_clean("encode", c);
+  return rc;
+}
+
+// decode from the blocks outside `lost`, each a separate buffer, listed in reverse
+int decode_case(const Case& c, const std::vector<int>& lost) {
+  std::vector<int> ids;
+  std::vector<const uint8_t*> ptrs;
+  for (int id = c.k + c.m - 1; id >= 0; --id) {
+    bool gone = false;
+    for (int x : lost) gone |= x == id;
+    if (!gone) {
+      ids.push_back(id);
+      ptrs.push_back(block(c, id));
+    }
+  }
+  std::vector<uint8_t> out(c.size + 1);
+  const int rc = leoec_decode(c.coding, c.k, c.m, c.w, ptrs.data(), ids.data(), (int)ids.size(),
+                              c.bs, c.size, out.data());
+  if (rc || std::memcmp(out.data(), c.data.data(), c.size))
+    fail("decode " + name(c) + " rc " + std::to_string(rc));
+  slot_clean("decode", c);
+  return rc;
+}
+
 // encode, decode (m blocks lost, survivors listed in reverse), repair of two
 // blocks; t picks the erasure pattern
 void roundtrip(const Case& c, int t, bool with_repair = true) {
   const int k = c.k, m = c.m, n = k + m;
   const uint64_t bs = c.bs;
-  {
-    std::vector<uint8_t> out((size_t)(n - c.filled) * bs + 1);
-    const int rc = leoec_encode(c.coding, k, m, c.w, c.data.data(), c.size, out.data(), out.size());
-    if (rc || std::memcmp(out.data(), block(c, c.filled), (size_t)(n - c.filled) * bs))
-      fail("encode " + name(c) + " rc " + std::to_string(rc));
-  }
-  std::vector<int> lost, ids;
+  encode_case(c);
+  std::vector<int> lost;
   for (int j = 0; j < m; ++j) {
     const int id = (t * 7 + j * 3) % n;
     bool dup = false;
     for (int x : lost) dup |= x == id;
     if (!dup) lost.push_back(id);
   }
-  for (int id = n - 1; id >= 0; --id) {
-    bool gone = false;
-    for (int x : lost) gone |= x == id;
-    if (!gone) ids.push_back(id);
-  }
-  {
-    std::vector<const uint8_t*> ptrs;
-    for (int id : ids) ptrs.push_back(block(c, id));
-    std::vector<uint8_t> out(c.size + 1);
-    const int rc = leoec_decode(c.coding, k, m, c.w, ptrs.data(), ids.data(), (int)ids.size(), bs,
-                                c.size, out.data());
-    if (rc || std::memcmp(out.data(), c.data.data(), c.size))
-      fail("decode " + name(c) + " rc " + std::to_string(rc));
-  }
+  decode_case(c, lost);
   if (with_repair) {
     const int rep[2] = {t % n, (t + 5) % n};
     const int nrep = rep[0] == rep[1] ? 1 : 2;
@@ -126,6 +151,7 @@ void roundtrip(const Case& c, int t, bool with_repair = true) {
     for (int r = 0; ok && r < nrep; ++r)
       ok = !std::memcmp(out.data() + (size_t)r * bs, block(c, rep[r]), bs);
     if (!ok) fail("repair " + name(c) + " rc " + std::to_string(rc));
+    slot_clean("repair", c);
   }
 }
 
@@ -268,10 +294,81 @@ int main(int argc, char** argv) {
       if (rc != LEOEC_E_HIP || left != 0)
         fail("injected event failure at chunk 1: rc " + std::to_string(rc) + ", " +
              std::to_string(left) + " creations short of it");
+      // the failure the call reported is its own: it may stay in the slot
+      // (a caller that goes on clears it, as here)
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess && e != hipErrorOutOfMemory)
+        fail("injected event failure: slot holds " + std::to_string((int)e));
       for (int r = 0; r < 3; ++r) roundtrip(r == 1 ? c : d, r, false);
     });
     t.join();
     std::printf("chunk-1 event failure: %s\n", g_errs.empty() ? "ok" : "FAILED");
+  }
+
+  // phase 2c: HIP failures the engine recovers from leave nothing behind.
+  // One thread, three calls, each after an injected failure that makes the
+  // staging fall back to a copy form; each must return LEOEC_OK, be bit-exact
+  // and leave the thread's last-error slot clean (encode_case / decode_case
+  // check all three).  fake_kernels.cpp's launchers report LEOEC_E_HIP when
+  // the slot is not clean, as a launcher reading the sticky slot would.
+  {
+    Case small{LEOEC_VANDRS, 10, 4, 8, 65543};
+    // span (k + m) bs = 2.24 MiB: above the 2 MiB mapped buffers of the pool,
+    // so a thread holding one has to grow it (engine.cpp zc_ready)
+    Case grow{LEOEC_VANDRS, 10, 4, 8, 1677721 + 3};
+    Case over{LEOEC_VANDRS, 10, 4, 8, (16u << 20) + 5};  // above the zero-copy cap
+    prepare(&small, 51);
+    prepare(&grow, 52);
+    prepare(&over, 53);
+    std::thread t([&] {
+      auto unused = [](const char* what, int left) {
+        if (left != 0) fail(std::string(what) + ": the injected failure was not reached");
+      };
+      // Where each failure lands is pinned by the order of the thread's
+      // allocations in a per-thread call (engine.cpp stage_for: zc_ready's
+      // mapped buffer first; then, for separate input blocks, gather_buf's
+      // pinned buffer) and by counting: between arming and the check the
+      // thread makes exactly the hipHostMalloc calls listed at each step,
+      // the failing ones first, so no other allocation site took a failure.
+      auto mallocs = [](const char* what, long before, long want) {
+        const long got = fakehip::host_malloc_calls() - before;
+        if (got != want)
+          fail(std::string(what) + ": " + std::to_string(got) + " hipHostMalloc calls, expected " +
+               std::to_string(want));
+      };
+      // (a) zero-copy: the thread takes a pooled mapped buffer, then needs a
+      // larger one, and its hipHostMalloc fails: pageable copies instead
+      encode_case(small);
+      long calls = fakehip::host_malloc_calls();
+      fakehip::fail_nth_host_malloc(1);
+      encode_case(grow);
+      unused("zc_ready hipHostMalloc", fakehip::fail_host_malloc_in());
+      mallocs("zc_ready hipHostMalloc", calls, 1);
+      // (b) gather: a decode from k separate survivor buffers; the mapped
+      // buffer cannot be had (first failure), nor the pinned gather buffer of
+      // the survivors (second, engine.cpp gather_buf in stage_h2d_segs): one
+      // pageable copy each.  The four rebuilt blocks then come back through
+      // gather_buf again (stage_d2h_sync_impl), whose allocation succeeds:
+      // the third and last hipHostMalloc of the call
+      calls = fakehip::host_malloc_calls();
+      fakehip::fail_nth_host_malloc(1, 2);
+      decode_case(grow, {0, 3, 7, 9});
+      unused("gather_buf hipHostMalloc", fakehip::fail_host_malloc_in());
+      mallocs("zc_ready + gather_buf hipHostMalloc", calls, 3);
+      // (c) a call above the cap after a small call whose mapped buffer got
+      // no device address (zc_ready's hipHostGetDevicePointer, the only one a
+      // data call makes; its one hipHostMalloc before it succeeds)
+      calls = fakehip::host_malloc_calls();
+      fakehip::fail_nth_host_get_device_pointer(1);
+      encode_case(grow);
+      unused("zc_ready hipHostGetDevicePointer", fakehip::fail_host_get_device_pointer_in());
+      mallocs("zc_ready hipHostGetDevicePointer", calls, 1);
+      decode_case(over, {2});
+      fakehip::fail_nth_host_malloc(0);
+      fakehip::fail_nth_host_get_device_pointer(0);
+    });
+    t.join();
+    std::printf("recovered HIP failures: %s\n", g_errs.empty() ? "ok" : "FAILED");
   }
 
   // phase 3: plan-cache churn: every 4-erasure pattern of vandrs(10,4,8)
@@ -303,6 +400,7 @@ int main(int argc, char** argv) {
                                             c.size, out.data());
                 if (rc || std::memcmp(out.data(), c.data.data(), c.size))
                   fail("pattern decode rc " + std::to_string(rc));
+                slot_clean("pattern decode", c);
               }
         for (int r = 0; r < 40; ++r) {
           // distinct lost pairs of the 32-block cauchyrs code: distinct plans
@@ -322,6 +420,7 @@ int main(int argc, char** argv) {
           if (rc || std::memcmp(out.data(), block(cb, x), cb.bs) ||
               std::memcmp(out.data() + cb.bs, block(cb, y), cb.bs))
             fail("bitmatrix repair rc " + std::to_string(rc));
+          slot_clean("bitmatrix repair", cb);
         }
       });
     for (auto& x : th) x.join();

@@ -5,9 +5,11 @@ engine.cpp / hostq.cpp / capi.cpp / codes.cpp / knobs.cpp with g++ against a
 CPU stand-in for the HIP runtime (asynchronous in-order streams with random
 delays, events, pinned vs pageable copies, two devices) and CPU kernels, and
 host_stress.cpp drives the C ABI from many threads, comparing every result
-with the oracle.  Round 3's verdict asked for this in place of re-running
-the GPU suite to reproduce round 2's silent host-side abort ("The
-round-2 abort")."""
+with the oracle.  The stand-in models HIP's per-thread sticky last-error slot
+and injects allocation failures: every call must leave the slot clean, also
+after a failure the engine recovered from (host_stress.cpp phase 2c).  Round
+3's verdict asked for this in place of re-running the GPU suite to reproduce
+round 2's silent host-side abort ("The round-2 abort")."""
 import os
 import subprocess
 
@@ -37,4 +39,5 @@ def test_host_side_under_sanitizers(built, binary, threads, rounds):
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-6000:]
     assert "host_stress: all results bit-exact" in r.stdout
+    assert "recovered HIP failures: ok" in r.stdout  # phase 2c ran (injected allocation failures)
     assert "WARNING: ThreadSanitizer" not in out and "runtime error" not in out, out[-6000:]
