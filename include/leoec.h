@@ -360,7 +360,90 @@ int leoec_scrub_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj
                     uint32_t *report, uint32_t *totals, void *workspace, uint64_t workspace_bytes,
                     void *stream);
 
+/* Workspace bytes leoec_scrub_ws_dev wants for this batch: leoec_scrub_dev's
+ * for everything that call serves; for cauchyrs and liberation
+ * 16 + round_up(4 * nobj, 16) + nobj * m * block_size (one pass);
+ * LEOEC_E_BAD_SIZE when that overflows; bytes == NULL: LEOEC_E_ARG.
+ * Configurations leoec_scrub_ws_dev does not serve, and invalid ones, get its
+ * statuses.  Needs no device. */
+int leoec_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                 uint64_t *bytes);
+
+/* leoec_scrub_dev with an encode region in its workspace, which adds the
+ * bitmatrix classes, in the relation leoec_locate_ws_dev has to
+ * leoec_locate_dev.  The contract is the composition leoec_locate_ws_dev then
+ * leoec_heal_dev(lost = report), byte for byte: after the call
+ *   report[o]  is leoec_locate_ws_dev's word for object o of the batch as it
+ *              was before the call: 0, one bit b < k + m, or LEOEC_LOCATE_MANY;
+ *   objs and parity hold the bytes leoec_heal_dev(..., lost = report, ...)
+ *              leaves: every object whose word names one block has that block
+ *              rebuilt in place from its first k intact ids ascending, data
+ *              blocks clipped to `size`, bytes past `size` read as zero and
+ *              never touched; a clean object and a LEOEC_LOCATE_MANY object
+ *              are not written at all;
+ *   totals[0]  is the number of objects named and rebuilt, totals[1] the number
+ *              of LEOEC_LOCATE_MANY objects; both words are overwritten.
+ * Layout, alignment and stride rules are leoec_scrub_dev's.
+ * Served:
+ *   (a) everything leoec_scrub_dev serves: the call and the query are
+ *       forwarded to it, with the same workspace size, statuses and bytes;
+ *   (b) cauchyrs and liberation with m >= 2, k + m <= 31 and
+ *       (m-1) * k * w <= 768: leoec_locate_ws_dev's class (b) less k + m = 32,
+ *       where the bit of id 31 is LEOEC_LOCATE_MANY's own word, so an object
+ *       that names block 31 and one that names none could not be told apart
+ *       and the totals could not be counted.
+ * Everything else (vandrs w = 16 / 32, w = 8 with k > 16 or m > 4 or m = 1,
+ * bitmatrix m = 1, k + m >= 32, a table above 768 words such as
+ * cauchyrs(10,4,32)) is LEOEC_E_UNSUPPORTED, returned before the device is
+ * opened; invalid parameters keep their leoec_check_params status; nobj == 0
+ * is LEOEC_OK with nothing written.  The checks come in leoec_scrub_dev's
+ * order: layout and parameters, served, empty batch, pointers and strides,
+ * then the device.
+ * workspace for (b): device, 16-byte aligned: a 16-byte header, then
+ * round_up(4 * nobj, 16) bytes of index words, then the encode region.  The
+ * query's size holds every object's m coding blocks (one pass); the call takes
+ * anything down to 16 + round_up(4 * nobj, 16) + m * block_size and then works
+ * in chunks of objects on the same stream, with the same results.
+ * workspace_bytes below that minimum, report, totals or workspace NULL or
+ * misaligned (4, 4 and 16 bytes), or report or totals inside the workspace:
+ * LEOEC_E_ARG.  The workspace's contents after the call are unspecified.
+ * What runs for (b), per chunk, on `stream`: the class's encode into the
+ * workspace, a memset, leoec_locate_ws_dev's launch, one launch that writes
+ * the final words, lists the objects that name a block and adds to the totals,
+ * and one launch of fixed size that rebuilds the listed objects' blocks packet
+ * by packet from the code's block table (leoec_scrub_bitrows).  Nothing is
+ * allocated, uploaded or waited for, so the call can be captured into a
+ * graph, after the first call: the first call of a code on a device builds
+ * that table on the host (k + m records, under 100 KB), uploads it with a
+ * blocking copy and loads the code objects (1-2 ms each); the leoec_gf_init
+ * warm-up does not cover them.  The table cache holds 16 tables per process
+ * and is its own, beside leoec_heal_dev's; past that the call runs
+ * leoec_locate_ws_dev then leoec_heal_dev's other path, which brings the masks
+ * back to the host (one stream synchronisation), rebuilds runs of consecutive
+ * objects with the same mask and fills the workspace's index words from the
+ * host.
+ * The limit at m = 2 is leoec_locate_ws_dev's and holds for every liberation
+ * call: two damaged blocks may be reported as a third, which is then
+ * "healed". */
+int leoec_scrub_ws_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                       uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                       uint32_t *report, uint32_t *totals, void *workspace,
+                       uint64_t workspace_bytes, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
+
+/* The map leoec_scrub_ws_dev rebuilds one lost block of a cauchyrs or
+ * liberation object with; needs no device.  surv[0..k): the first k ids
+ * ascending without `block`, leoec_decode_dev's survivors.  rows
+ * (cap >= w * ceil(k*w / 32) words): row r is ceil(k*w / 32) words; bit
+ * i*w + c of the row (word (i*w + c) / 32, bit (i*w + c) % 32) is set iff
+ * packet c of block surv[i] feeds packet r of `block`.  A block outside
+ * 0..k+m-1: LEOEC_E_BAD_ID; surv or rows NULL or cap too small: LEOEC_E_ARG.
+ * Serves class (b) of leoec_scrub_ws_dev only and gives its statuses
+ * otherwise; vandrs and isars are LEOEC_E_UNSUPPORTED (their map is
+ * leoec_heal_rows). */
+int leoec_scrub_bitrows(int coding, int k, int m, int w, int block, int *surv, uint32_t *rows,
+                        int cap);
 
 /* The GF(2) ratios leoec_locate_ws_dev tests the syndromes of cauchyrs and
  * liberation with; needs no device.  rows (cap >= (m-1) * k * w words): word

@@ -21,7 +21,8 @@
 //   locate_finish.
 // Everything leoec_locate_dev serves is forwarded to it.
 // leoec_scrub_dev (scrub.hip) runs op_locate_dev with its own steps in it
-// (scrub_steps.hpp): its kernel stands in locate_finish's place.
+// (scrub_steps.hpp): its kernel stands in locate_finish's place;
+// leoec_scrub_ws_dev does the same with op_locate_ws_dev's bitmatrix branch.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
@@ -224,7 +225,12 @@ bit_locate(const BitLocArgs a, uint32_t* __restrict__ lost) {
   if (threadIdx.x == 0u) atomicAnd(&lost[obj], mask);
 }
 
+}  // namespace
+
+// (scrub_steps.hpp: scrub.hip asks too)
 bool bit_class(int coding) { return coding == LEOEC_CAUCHYRS || coding == LEOEC_LIBERATION; }
+
+namespace {
 
 bool bit_locate_served(int coding, int k, int m, int w) {
   return bit_class(coding) && m >= 2 && k + m <= 32 && (m - 1) * k * w <= kBitLocWords;
@@ -268,9 +274,15 @@ int op_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, u
   return LEOEC_OK;
 }
 
+}  // namespace
+
+// steps (scrub_steps.hpp): leoec_scrub_ws_dev's share of the bitmatrix branch,
+// with `workspace` its encode region alone (the chunk size comes from
+// workspace_bytes); none for leoec_locate_ws_dev itself.
 int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
                      uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
-                     uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+                     uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s,
+                     LocateSteps* steps) {
   uint64_t bs;
   int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
   if (rc) return rc;
@@ -282,10 +294,12 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
   if ((rc = bit_locate_code(coding, k, m, w, &c, &rows))) return rc;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
   if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if (steps && (rc = steps->check(bs))) return rc;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
   if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per) return LEOEC_E_ARG;
   if ((rc = device_init())) return rc;
+  if (steps && (rc = steps->begin(*c, s))) return rc;
   std::vector<Shard> in(k);
   std::vector<int> surv(k), want(m);
   for (int j = 0; j < k; ++j) {
@@ -327,6 +341,10 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
     if (launch_kernel(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s, a,
                       lost + o0) != LEOEC_OK)
       return LEOEC_E_HIP;
+    if (steps) {
+      if ((rc = steps->finish(o0, no, s))) return rc;
+      continue;
+    }
     if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
                       dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
       return LEOEC_E_HIP;
@@ -334,7 +352,6 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
   return LEOEC_OK;
 }
 
-}  // namespace
 }  // namespace leoec
 
 extern "C" {
@@ -351,7 +368,7 @@ int leoec_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, ui
   return leoec::guarded([&] {
     return leoec::op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
                                    parity_stride, lost, workspace, workspace_bytes,
-                                   (hipStream_t)stream);
+                                   (hipStream_t)stream, nullptr);
   });
 }
 

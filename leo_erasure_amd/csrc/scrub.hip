@@ -16,13 +16,33 @@
 // When heal's table cache is full (heal.hip) the call is the composition
 // itself: op_locate_dev with scrub_finish counting only, then op_heal_dev's
 // generic path with the index words as its `unhealed`, which synchronises once.
+//
+// leoec_scrub_ws_dev adds the bitmatrix classes (cauchyrs, liberation, m >= 2,
+// k + m <= 31, (m - 1) k w <= 768) and forwards everything else to
+// leoec_scrub_dev.  Per chunk of objects that the encode region holds:
+//   locate          op_locate_ws_dev's encode, memset and bit_locate;
+//   scrub_finish    as above;
+//   bit_heal_list   (scrub_bit_impl.hpp) one named block of every listed
+//                   object from the code's block table (scrub_bit_table.hpp),
+//                   from a fixed grid.
+// Workspace: the 16-byte header, one index word per object (rounded up to 16
+// bytes), then the encode region, m bs bytes per object of a chunk.  The block
+// tables are cached per (code, device) as heal's are, in a cache of their own;
+// when it is full the call is the composition: op_locate_ws_dev with
+// scrub_finish counting only, then op_heal_dev's generic path.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
+#include <map>
+#include <memory>
+#include <mutex>
+#include <tuple>
 #include <utility>
+#include <vector>
 
 #include "engine.hpp"
 #include "knobs.hpp"
+#include "scrub_bit_impl.hpp"
 #include "scrub_impl.hpp"
 #include "scrub_steps.hpp"
 
@@ -57,7 +77,9 @@ scrub_finish(uint32_t* __restrict__ words, uint32_t n, uint32_t* __restrict__ li
   const uint32_t v = in ? words[i] : 0xFFFFFFFFu;
   const uint32_t f = v == 0xFFFFFFFFu ? 0u : (v != 0u && (v & (v - 1u)) == 0u) ? v : LEOEC_LOCATE_MANY;
   if (in) words[i] = f;
-  // (with k + m <= 20 no single-bit word is LEOEC_LOCATE_MANY's own bit)
+  // (no single-bit word is LEOEC_LOCATE_MANY's own bit: k + m <= 20 for
+  // leoec_scrub_dev, <= 31 for leoec_scrub_ws_dev, which refuses k + m = 32
+  // for this line's sake)
   const bool many = f == LEOEC_LOCATE_MANY;
   const bool one = f != 0u && !many;
   const uint64_t b1 = __builtin_amdgcn_ballot_w64(one);
@@ -198,6 +220,227 @@ int op_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_st
                      st.list(), s);
 }
 
+// ---------------------------------------------------------------------------
+// The bitmatrix classes: leoec_scrub_ws_dev.
+
+// A cauchyrs or liberation configuration: leoec_locate_ws_dev's statuses (an
+// empty batch with no buffers goes through its layout, parameter and served
+// tests and ends there: no device), then k + m = 32, where id 31's bit is
+// LEOEC_LOCATE_MANY's own and the totals could not be counted.
+int bit_scrub_served(int coding, int k, int m, int w, uint64_t size) {
+  const int rc = op_locate_ws_dev(coding, k, m, w, nullptr, 0, size, 0, nullptr, 0, nullptr, nullptr,
+                                  0, nullptr, nullptr);
+  if (rc) return rc;
+  return scrub_bit_shape(k, m, w);
+}
+
+int scrub_bit_fn(const Code& c, const int* surv, int block, std::vector<uint8_t>* rows) {
+  return bit_rows(c, surv, &block, 1, rows);
+}
+
+// The block tables on the devices: one per (coding, k, m, w, device), built
+// and uploaded at the first scrub that needs it and kept for the process, as
+// heal.hip keeps its pattern tables and beside them: never evicted (a queued
+// launch may still be reading one), bounded by count (at most 16 x 95 KB of
+// device memory), past which the caller runs the composition.
+constexpr size_t kMaxScrubBitTables = 16;
+
+struct ScrubBitTable {
+  std::vector<uint32_t> host;
+  uint32_t* dev = nullptr;
+};
+
+// LEOEC_OK and *out = the device image, or *out = nullptr when the cache is
+// full; a status when the build or the upload failed.
+int scrub_bit_table(const Code& c, const uint32_t** out) {
+  static std::mutex mu;
+  static auto* cache =
+      new std::map<std::tuple<int, int, int, int, int>, std::unique_ptr<ScrubBitTable>>;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return LEOEC_E_HIP;
+  const auto key = std::make_tuple(c.coding, c.k, c.m, c.w, dev);
+  std::lock_guard<std::mutex> lock(mu);
+  const auto it = cache->find(key);
+  if (it != cache->end()) {
+    *out = it->second->dev;
+    return LEOEC_OK;
+  }
+  *out = nullptr;
+  if (cache->size() >= kMaxScrubBitTables) return LEOEC_OK;
+  std::unique_ptr<ScrubBitTable> t(new ScrubBitTable);
+  const int rc = scrub_bit_build_table(
+      c.k, c.m, c.w,
+      [&c](const int* surv, int block, std::vector<uint8_t>* rows) {
+        return scrub_bit_fn(c, surv, block, rows);
+      },
+      &t->host);
+  if (rc) return rc;
+  const size_t bytes = t->host.size() * sizeof(uint32_t);
+  if (hipMalloc(&t->dev, bytes) != hipSuccess) return LEOEC_E_NOMEM;
+  // a blocking copy: the image is on the device before any launch reads it
+  if (hipMemcpy(t->dev, t->host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    hip_drop(hipFree(t->dev));
+    return LEOEC_E_HIP;
+  }
+  *out = t->dev;
+  cache->emplace(key, std::move(t));
+  return LEOEC_OK;
+}
+
+// Header and index words for nobj objects plus an encode region of `enc`
+// bytes; false when that overflows.
+bool scrub_ws_workspace(uint64_t nobj, uint64_t enc, uint64_t* bytes) {
+  uint64_t head;
+  return scrub_workspace(nobj, &head) && !__builtin_add_overflow(head, enc, bytes);
+}
+
+int op_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                              uint64_t* bytes) {
+  if (!bit_class(coding)) return op_scrub_dev_workspace(coding, k, m, w, size, nobj, bytes);
+  int rc = bit_scrub_served(coding, k, m, w, size);
+  if (rc) return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  uint64_t bs = 0, per, enc;
+  if ((rc = op_layout(coding, k, m, w, size, &bs, nullptr))) return rc;
+  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &enc))
+    return LEOEC_E_BAD_SIZE;
+  return scrub_ws_workspace(nobj, enc, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
+}
+
+// leoec_scrub_ws_dev's share of op_locate_ws_dev's bitmatrix branch.
+struct BitScrubSteps final : LocateSteps {
+  int k = 0, m = 0, w = 0;
+  uint8_t* objs = nullptr;
+  uint64_t obj_stride = 0, size = 0, bs = 0, nobj = 0;
+  uint8_t* parity = nullptr;
+  uint64_t parity_stride = 0;
+  uint32_t* report = nullptr;
+  uint32_t* totals = nullptr;
+  void* workspace = nullptr;
+  uint64_t workspace_bytes = 0;
+  bool begun = false;               // begin() ran: the device is open
+  const uint32_t* table = nullptr;  // nullptr after begin(): the cache is full
+
+  uint32_t* header() const { return static_cast<uint32_t*>(workspace); }
+  uint32_t* list() const { return header() + kScrubHeader / sizeof(uint32_t); }
+
+  int check(uint64_t block_size) override {
+    bs = block_size;
+    if (!totals || ((uintptr_t)totals & 3u)) return LEOEC_E_ARG;
+    if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
+    uint64_t per, need;  // the header, the index words and one object's encode
+    if (__builtin_mul_overflow((uint64_t)m, bs, &per) || !scrub_ws_workspace(nobj, per, &need))
+      return LEOEC_E_BAD_SIZE;
+    if (workspace_bytes < need) return LEOEC_E_ARG;
+    if (overlaps(report, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
+        overlaps(totals, 2 * sizeof(uint32_t), workspace, workspace_bytes))
+      return LEOEC_E_ARG;
+    return LEOEC_OK;
+  }
+
+  int begin(const Code& c, hipStream_t s) override {
+    const int rc = scrub_bit_table(c, &table);
+    if (rc) return rc;
+    begun = true;
+    return hipMemsetAsync(totals, 0, 2 * sizeof(uint32_t), s) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+  }
+
+  int finish(uint64_t o0, uint64_t no, hipStream_t s) override {
+    uint32_t* const words = report + o0;
+    if (table && hipMemsetAsync(header(), 0, kScrubHeader, s) != hipSuccess) return LEOEC_E_HIP;
+    // no <= 2^31 - 1 words: one grid
+    if (launch_kernel(scrub_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                      dim3(kThreads), 0, s, words, (uint32_t)no, table ? list() : nullptr, header(),
+                      totals) != LEOEC_OK)
+      return LEOEC_E_HIP;
+    if (!table) return LEOEC_OK;
+    BitHealArgs a;
+    a.h.objs = objs + o0 * obj_stride;
+    a.h.obj_stride = obj_stride;
+    a.h.parity = parity + o0 * parity_stride;
+    a.h.parity_stride = parity_stride;
+    a.h.lost = words;
+    a.h.unhealed = nullptr;
+    a.h.table = table;
+    a.h.size = size;
+    a.h.bs = (uint32_t)bs;  // < 2^32 (check_dev_batch), a multiple of 16 w
+    a.h.k = (uint32_t)k;
+    a.h.m = (uint32_t)m;
+    a.w = (uint32_t)w;
+    a.ps = (uint32_t)(bs / (uint64_t)w);
+    a.h.tiles = (a.ps + kBitHealTile - 1u) / kBitHealTile;  // bit_locate's: no x tiles < 2^31
+    a.h.nobj = (uint32_t)no;
+    a.h.tmap = a.h.tperm = 0;
+    a.rec_words = scrub_bit_record_words(k, w);
+    a.pad = 0;
+    const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
+    return launch_bit_heal_list(a, list(), header(), cap, s);
+  }
+};
+
+int op_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                    uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                    uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
+                    hipStream_t s) {
+  if (!bit_class(coding))  // served or LEOEC_E_UNSUPPORTED there
+    return op_scrub_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                        totals, workspace, workspace_bytes, s);
+  int rc = bit_scrub_served(coding, k, m, w, size);
+  if (rc) return rc;
+  BitScrubSteps st;
+  st.k = k;
+  st.m = m;
+  st.w = w;
+  st.objs = objs;
+  st.obj_stride = obj_stride;
+  st.size = size;
+  st.nobj = nobj;
+  st.parity = parity;
+  st.parity_stride = parity_stride;
+  st.report = report;
+  st.totals = totals;
+  st.workspace = workspace;
+  st.workspace_bytes = workspace_bytes;
+  // the encode region behind the header and the index words (check() refuses
+  // a workspace that has none before anything looks at it)
+  uint64_t head;
+  void* enc = nullptr;
+  uint64_t enc_bytes = 0;
+  if (workspace && scrub_workspace(nobj, &head) && workspace_bytes > head) {
+    enc = static_cast<uint8_t*>(workspace) + head;
+    enc_bytes = workspace_bytes - head;
+  }
+  rc = op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                        enc, enc_bytes, s, &st);
+  if (rc || !st.begun || st.table) return rc;
+  // the table cache is full: the words are final and counted; the rest is
+  // leoec_heal_dev's generic path (one synchronisation)
+  return op_heal_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                     st.list(), s);
+}
+
+int op_scrub_bitrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* rows,
+                     int cap) {
+  int rc = check_params(coding, k, m, w);
+  if (rc) return rc;
+  if (!bit_class(coding)) return LEOEC_E_UNSUPPORTED;
+  if ((rc = bit_scrub_served(coding, k, m, w, 0))) return rc;
+  if (block < 0 || block >= k + m) return LEOEC_E_BAD_ID;
+  if (!surv || !rows || cap < w * scrub_bit_row_words(k, w)) return LEOEC_E_ARG;
+  const Code* c;
+  if ((rc = get_code(coding, k, m, w, &c))) return rc;
+  std::vector<int> sv(k);
+  std::vector<uint32_t> t;
+  rc = scrub_bit_rows(
+      k, m, w, block,
+      [c](const int* s, int b, std::vector<uint8_t>* out) { return scrub_bit_fn(*c, s, b, out); },
+      sv.data(), &t);
+  if (rc) return rc;
+  for (int i = 0; i < k; ++i) surv[i] = sv[i];
+  for (size_t i = 0; i < t.size(); ++i) rows[i] = t[i];
+  return LEOEC_OK;
+}
+
 }  // namespace
 }  // namespace leoec
 
@@ -217,6 +460,29 @@ int leoec_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj
     return leoec::op_scrub_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
                                report, totals, workspace, workspace_bytes, (hipStream_t)stream);
   });
+}
+
+int leoec_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                 uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_scrub_ws_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                       uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                       uint32_t* report, uint32_t* totals, void* workspace,
+                       uint64_t workspace_bytes, void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_scrub_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                  parity_stride, report, totals, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+  });
+}
+
+int leoec_scrub_bitrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* rows,
+                        int cap) {
+  return leoec::guarded(
+      [&] { return leoec::op_scrub_bitrows(coding, k, m, w, block, surv, rows, cap); });
 }
 
 }  // extern "C"

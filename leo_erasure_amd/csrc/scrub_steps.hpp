@@ -1,6 +1,7 @@
-// scrub_steps.hpp — what scrub.hip (leoec_scrub_dev) takes from locate.hip
-// and heal.hip: the locate call with the caller's own steps in it, the heal
-// call and heal's pattern table.  Internal to those three units.
+// scrub_steps.hpp — what scrub.hip (leoec_scrub_dev, leoec_scrub_ws_dev) takes
+// from locate.hip and heal.hip: the locate calls with the caller's own steps
+// in them, the heal call and heal's pattern table.  Internal to those three
+// units.
 #pragma once
 
 #include "engine.hpp"
@@ -28,6 +29,21 @@ struct LocateSteps {
 int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
                   uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
                   uint32_t* lost, hipStream_t s, LocateSteps* steps);
+
+// locate.hip: cauchyrs or liberation, the classes of leoec_locate_ws_dev's
+// bitmatrix branch.
+bool bit_class(int coding);
+
+// locate.hip; steps == nullptr: leoec_locate_ws_dev.  The steps stand in the
+// bitmatrix branch (cauchyrs, liberation) at the same three places: check
+// after the served test, the empty batch and `lost`'s check, begin once the
+// device is open, finish(o0, no, s) in locate_finish's place after the
+// chunk's encode, memset and bit_locate.  `workspace` is the encode region:
+// the chunk size comes from workspace_bytes.
+int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                     uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s,
+                     LocateSteps* steps);
 
 // heal.hip: leoec_heal_dev, and the code's pattern table on the current
 // device: LEOEC_OK and *out = the device image, or *out = nullptr when the

@@ -274,6 +274,68 @@ def scrub(coding, params, objs, size, parity, nobj=None, report=None, totals=Non
     return report, totals
 
 
+def scrub_ws_workspace(coding, params, size, nobj):
+    """leoec_scrub_ws_dev_workspace: bytes of workspace scrub_ws() wants for one
+    pass over the batch: scrub_workspace()'s for everything scrub() serves; for
+    cauchyrs and liberation the header, one index word per object and the
+    encode region of ``nobj`` objects."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_scrub_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
+                                                ctypes.byref(out)))
+    return out.value
+
+
+def scrub_ws(coding, params, objs, size, parity, nobj=None, report=None, totals=None,
+             workspace=None, stream=None):
+    """leoec_scrub_ws_dev: scrub(), also for cauchyrs and liberation (m >= 2,
+    k + m <= 31, (m - 1) k w <= 768): locate_ws() then heal() in one call.
+    Returns ``(report, totals)`` as scrub() does.  ``workspace`` (uint8) follows
+    locate_ws()'s rules: allocated when not given, its encode region up to
+    ``VERIFY_WORKSPACE_CAP`` (a smaller workspace than ``scrub_ws_workspace()``
+    gives the same results in more chunks of objects), and required on an
+    explicit ``stream``."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    if report is None:
+        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    if totals is None:
+        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
+    _words(report, nobj, "report")
+    _words(totals, 2, "totals")
+    need = scrub_ws_workspace(coding, params, size, nobj)
+    if workspace is None:
+        head = 16 + (4 * nobj + 15) // 16 * 16
+        if stream is not None:
+            raise ValueError("scrub_ws on an explicit stream needs an explicit workspace "
+                             f"({need} B for one pass)")
+        enc = need - head  # 0 for everything scrub() serves
+        if enc:
+            enc = max(min(enc, VERIFY_WORKSPACE_CAP), m * bs)
+        workspace = torch.empty(head + enc, dtype=torch.uint8, device=objs.device)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    _lib.check(lib.leoec_scrub_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
+                                      size, nobj, parity.data_ptr(), _row_stride(parity),
+                                      report.data_ptr(), totals.data_ptr(), workspace.data_ptr(),
+                                      workspace.numel(), _stream(stream)))
+    return report, totals
+
+
+def scrub_bitrows(coding, params, block):
+    """leoec_scrub_bitrows (no device needed): the map scrub_ws() rebuilds block
+    ``block`` of a cauchyrs or liberation object with.  Returns ``(surv, rows)``:
+    the k survivor ids (the first k ids ascending without ``block``) and w
+    lists of ``ceil(k w / 32)`` words, bit ``i w + c`` of row r set iff packet c
+    of block ``surv[i]`` feeds packet r of ``block``."""
+    k, m, w = params
+    rw = (k * w + 31) // 32
+    cap = max(w * rw, 1)
+    surv = (ctypes.c_int * max(k, 1))()
+    rows = (ctypes.c_uint32 * cap)()
+    _lib.check(lib.leoec_scrub_bitrows(_cid(coding), k, m, w, block, surv, rows, cap))
+    return list(surv[:k]), [list(rows[r * rw:(r + 1) * rw]) for r in range(w)]
+
+
 def locate_bitrows(coding, params):
     """leoec_locate_bitrows (no device needed): the GF(2) ratios locate_ws()
     tests the syndromes of cauchyrs and liberation with: ``m - 1`` lists of k

@@ -1,0 +1,306 @@
+"""leoec_scrub_ws_dev on the device (product library): locate_ws and heal in
+one call for cauchyrs and liberation, on the edge harness of gpu_helpers
+(guarded arenas, random non-zero bytes behind every object, every byte of both
+arenas, the words around the covered ones and the workspace's tail compared
+after every call).
+
+The contract is the composition device.locate_ws then device.heal(lost =
+report); the batches are test_device_scrub.py's (scrub_helpers' position batch:
+object b of k + m + 2 has block b damaged, one object is clean, one has two
+damaged blocks; a clean batch; scrub_dev_helpers' dense batch), for the six
+bitmatrix families of locate_ws_helpers.FAMILIES at the sizes k B - 1 and
+16 w (k - 2) + 5 (every packet has whole 1 KiB tiles and a last partial one,
+the last data block is ragged at the first size, empty with the one before it
+ragged at the second) and at k B, where no block is clipped
+(scrub_ws_helpers.cases).  Expected words are by construction."""
+import contextlib
+import ctypes
+import os
+import subprocess
+import sys
+
+import pytest
+
+import gpu_helpers as H
+import locate_helpers as L
+import locate_ws_helpers as W
+import scrub_dev_helpers as D
+import scrub_helpers as S
+import scrub_ws_helpers as X
+
+
+@pytest.fixture(scope="module", params=W.FAMILIES, ids=W.family_id)
+def family(request):
+    """(module scope: the tests of one family run together and share its
+    EdgeCases, the oracle's blocks computed once per size)"""
+    return request.param
+
+
+# every family's packet has whole 1 KiB tiles and a last partial one
+assert all(B // w > X.TILE and (B // w) % X.TILE != 0 for _, _, _, w, B in W.FAMILIES)
+
+
+def _position(le, oracle, case):
+    dmg, _, locate = S.position_batch(case)
+    want = S.two_block_word(oracle, le, case, dmg, locate)
+    skip = None if want[-1] == S.MANY else case.n - 1
+    assert skip is None or case.m == 2
+    return dmg, want, skip
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_positions(gpu, le, oracle, family):
+    """One scrub of the position batch: the by-construction report between
+    intact sentinels, totals, every named object back to the snapshot, the
+    two-block object untouched.  Then the same damage through device.locate_ws
+    + device.heal: identical arenas and words, no object left out.  Then a
+    second scrub of the healed arenas: all zero but for the two-block object,
+    nothing rebuilt, no byte changed."""
+    errors = []
+    for case in X.cases(le, oracle, family):
+        dmg, want, skip = _position(le, oracle, case)
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        errors += X.check_scrub(gpu, le, case, work, par, want, skip)[1]
+        work, par, got, _, errs = X.check_equivalence(gpu, le, case, dmg)
+        errors += errs
+        if got != want:
+            errors.append(f"{case.ident()}: equivalence run's report {[hex(x) for x in got]}")
+        healed, par_healed = work.clone(), par.clone()
+        _, again, tot, errs = X.run_scrub(gpu, le, case, work, par)
+        errors += errs
+        ctx = f"second scrub_ws {case.ident()} bs {case.bs}"
+        # (m = 2 with a third block named: the other k + 1 blocks fit one
+        # another, so the rebuilt stripe is consistent, if wrong)
+        many = 1 if want[-1] == S.MANY else 0
+        expect = [0] * (case.n - 1) + [S.MANY if many else 0]
+        if again != expect or tot != [0, many]:
+            errors.append(f"{ctx}: report {[hex(x) for x in again]}, totals {tot}, expected "
+                          f"{[hex(x) for x in expect]}, {[0, many]}")
+        for err in (H.arena_diff(gpu, work, healed, case.guard, f"{ctx}: objs"),
+                    H.arena_diff(gpu, par, par_healed, 1, f"{ctx}: parity")):
+            if err:
+                errors.append(err)
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_clean_batch(gpu, le, oracle, family):
+    """Nothing damaged: every word 0, totals (0, 0), no byte written."""
+    errors = []
+    for case in X.cases(le, oracle, family):
+        work, par = L.damaged_arenas(gpu, case, [])
+        errors += X.check_scrub(gpu, le, case, work, par, [0] * case.n)[1]
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_dense_batch(gpu, le, oracle, family):
+    """Every object with one damaged block, object o block o mod (k + m): every
+    one named and rebuilt, and the two-call sequence leaves the same bytes."""
+    errors = []
+    for case in X.cases(le, oracle, family):
+        dmg, want = D.dense_batch(case)
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        errors += X.check_scrub(gpu, le, case, work, par, want)[1]
+        errors += X.check_equivalence(gpu, le, case, dmg)[4]
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_small_workspaces(gpu, le, oracle, family):
+    """The position batch with the minimum workspace (one object per chunk)
+    and with room for 3 objects: report, totals and arenas as with one pass."""
+    errors = []
+    for case in X.cases(le, oracle, family):
+        dmg, want, skip = _position(le, oracle, case)
+        ref_work, ref_par, ref_got, ref_tot, errs = X.check_equivalence(gpu, le, case, dmg)
+        errors += errs
+        for room in (1, 3):
+            work, par = L.damaged_arenas(gpu, case, dmg)
+            errors += X.check_scrub(gpu, le, case, work, par, want, skip, room=room)[1]
+            work, par = L.damaged_arenas(gpu, case, dmg)
+            _, got, tot, errs = X.run_scrub(gpu, le, case, work, par, room=room)
+            errors += errs
+            ctx = f"scrub_ws {case.ident()} bs {case.bs} room {room} against one pass"
+            if got != ref_got or tot != ref_tot:
+                errors.append(f"{ctx}: report {[hex(x) for x in got]}, totals {tot}")
+            for err in (H.arena_diff(gpu, work, ref_work, case.guard, f"{ctx}: objs"),
+                        H.arena_diff(gpu, par, ref_par, 1, f"{ctx}: parity")):
+                if err:
+                    errors.append(err)
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_forwards_the_fused_family(gpu, le, oracle):
+    """vandrs(10,4,8) through device.scrub_ws equals device.scrub: report,
+    totals and arenas."""
+    family = ("vandrs", 10, 4, 8, 8704)
+    assert family in L.FAMILIES
+    errors = []
+    for case in X.cases(le, oracle, family):
+        dmg, _, locate = S.position_batch(case)
+        want = S.two_block_word(oracle, le, case, dmg, locate)
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        errors += X.check_scrub(gpu, le, case, work, par, want)[1]
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        work2, par2 = work.clone(), par.clone()
+        _, got, tot, errs = X.run_scrub(gpu, le, case, work, par)
+        errors += errs
+        _, got2, tot2, errs = D.run_scrub(gpu, le, case, work2, par2)
+        errors += errs
+        ctx = f"scrub_ws against scrub {case.ident()}"
+        if (got, tot) != (got2, tot2):
+            errors.append(f"{ctx}: report {[hex(x) for x in got]} {tot}, scrub's "
+                          f"{[hex(x) for x in got2]} {tot2}")
+        for err in (H.arena_diff(gpu, work, work2, case.guard, f"{ctx}: objs"),
+                    H.arena_diff(gpu, par, par2, 1, f"{ctx}: parity")):
+            if err:
+                errors.append(err)
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_captured(gpu, le, oracle):
+    """The call is memsets and launches on the stream: captured into a graph
+    (after one plain call, which builds the block table and loads the code
+    objects) it replays to the same report, totals and arenas, and again after
+    the buffers are refilled with a differently damaged batch."""
+    family = W.FAMILIES[0]
+    cls, k, m, w, B = family
+    assert (cls, k, m, w) == ("cauchyrs", 10, 4, 8)
+    case = next(iter(D.position_cases(le, oracle, family)))
+    n, g = case.n, case.guard
+    snap, par_snap = case.dev(gpu)
+    dmg, want, skip = _position(le, oracle, case)
+    assert skip is None  # m >= 3: every word by construction
+    first, par_first = L.damaged_arenas(gpu, case, dmg)
+    work, par = first.clone(), par_first.clone()
+    errors = X.check_scrub(gpu, le, case, work, par, want)[1]
+    assert not errors, "\n".join(errors)
+
+    def expect(before, par_before, words):
+        o_want, p_want = snap.clone(), par_snap.clone()
+        for o, word in enumerate(words):
+            if word == S.MANY:
+                o_want[g + o], p_want[1 + o] = before[g + o], par_before[1 + o]
+        return o_want, p_want, [sum(1 for x in words if x not in (0, S.MANY)),
+                                sum(1 for x in words if x == S.MANY)]
+
+    work.copy_(first)
+    par.copy_(par_first)
+    report = gpu.full((n,), L.PREFILL, dtype=gpu.int32, device="cuda")
+    totals = gpu.full((2,), D.TOTALS_PREFILL, dtype=gpu.int32, device="cuda")
+    need = le.device.scrub_ws_workspace(cls, case.params, case.size, n)
+    ws = gpu.full((need,), D.WS_FILL, dtype=gpu.uint8, device="cuda")
+    gpu.cuda.synchronize()
+    graph = gpu.cuda.CUDAGraph()
+    with gpu.cuda.graph(graph):
+        le.device.scrub_ws(cls, case.params, work[g:g + n], case.size, par[1:1 + n], report=report,
+                           totals=totals, workspace=ws)
+    dense, dense_words = D.dense_batch(case)
+    second, par_second = L.damaged_arenas(gpu, case, dense)
+    for before, par_before, words in ((first, par_first, want), (second, par_second, dense_words),
+                                      (first, par_first, want)):
+        work.copy_(before)
+        par.copy_(par_before)
+        report.fill_(L.PREFILL)
+        totals.fill_(D.TOTALS_PREFILL)
+        graph.replay()
+        gpu.cuda.synchronize()
+        o_want, p_want, counts = expect(before, par_before, words)
+        assert D._u32(report) == words, [hex(x) for x in D._u32(report)]
+        assert D._u32(totals) == counts
+        assert not H.arena_diff(gpu, work, o_want, g, "replay: objs")
+        assert not H.arena_diff(gpu, par, p_want, 1, "replay: parity")
+
+
+# ---------------------------------------------------------------------------
+# A HIP error pending on the calling thread (test_pending_hip_error.py's way:
+# hipSetDevice(-1) through the library's own runtime handle, no torch call
+# between planting and the clear).
+
+HIP_SUCCESS, HIP_ERROR_INVALID_DEVICE = 0, 101
+
+
+class _Wrapped:
+    """device.py's `lib` with leoec_scrub_ws_dev wrapped."""
+
+    def __init__(self, real, call):
+        self._real, self._call = real, call
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        return self._call(fn) if name == "leoec_scrub_ws_dev" else fn
+
+
+@contextlib.contextmanager
+def _planted(gpu, le, calls):
+    rt = ctypes.CDLL(le._lib.library_path())
+    for f in (rt.hipSetDevice, rt.hipPeekAtLastError, rt.hipGetLastError):
+        f.restype = ctypes.c_int
+    rt.hipSetDevice.argtypes = [ctypes.c_int]
+
+    def wrap(fn):
+        def call(*args):
+            gpu.cuda.synchronize()  # every buffer allocated and filled: no torch call from here
+            try:
+                assert rt.hipSetDevice(-1) == HIP_ERROR_INVALID_DEVICE
+                assert rt.hipPeekAtLastError() == HIP_ERROR_INVALID_DEVICE
+                rc = fn(*args)
+                calls.append((rc, rt.hipPeekAtLastError()))
+            finally:
+                rt.hipGetLastError()
+            return rc
+        return call
+
+    dev = le.device
+    real = dev.lib
+    dev.lib = _Wrapped(real, wrap)
+    try:
+        yield rt
+    finally:
+        dev.lib = real
+        rt.hipGetLastError()
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_with_pending_error(gpu, le, oracle):
+    """A first plain call, then one with hipErrorInvalidDevice pending on the
+    thread: LEOEC_OK, the results right, the same code in the slot afterwards."""
+    cls, k, m, w = "cauchyrs", 6, 3, 4
+    B = (4096 // (16 * w) + 1) * 16 * w
+    case = H.edge_case(le, oracle, (cls, k, m, w), k * B - 17, n=3)
+    dmg, want = D.dense_batch(case)
+    work, par = L.damaged_arenas(gpu, case, dmg)
+    first = X.check_scrub(gpu, le, case, work, par, want)[1]
+    assert not first, "\n".join(first)
+    dmg = [e for o in range(3) for e in S._entries(case, o, k + o, S.VALUES[:S.HITS])]
+    want = [1 << (k + o) for o in range(3)]
+    work, par = L.damaged_arenas(gpu, case, dmg)
+    calls = []
+    with _planted(gpu, le, calls) as rt:
+        errors = X.check_scrub(gpu, le, case, work, par, want)[1]
+    assert calls == [(0, HIP_ERROR_INVALID_DEVICE)], calls
+    assert not errors, "\n".join(errors)
+    assert rt.hipPeekAtLastError() == HIP_SUCCESS
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_scrub_ws_with_full_table_cache_in_own_process(gpu, tmp_path):
+    """tests/scrub_ws_table_cache_child.py in a fresh process: 16 bitmatrix
+    configurations scrubbed first fill the block table cache, the scrub of a
+    17th then takes the composed path and must still equal locate_ws + heal
+    byte for byte."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log = str(tmp_path / "scrub_ws_table_cache.log")
+    env = dict(os.environ, LIBC_FATAL_STDERR_="1")
+    env.pop("LEOEC_LIBRARY", None)
+    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_ws_table_cache_child.py")]
+    with open(log, "w") as fh:
+        rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=280)
+    with open(log) as fh:
+        tail = fh.read()[-4000:]
+    assert rc == 0, f"scrub_ws_table_cache_child.py failed (rc {rc}), {log}:\n{tail}"
+    assert "17th configuration scrubbed" in tail, tail
