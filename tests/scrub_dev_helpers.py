@@ -2,8 +2,9 @@
 test_scrub_forms.py, scrub_table_cache_child.py): one device.scrub over
 arenas the caller damaged, with everything the call may not touch compared
 afterwards, the expectations of scrub_helpers' position batch and of the dense
-batch, and the two-call sequence device.locate + device.heal the call must
-equal byte for byte."""
+batch, the two-call sequence device.locate + device.heal the call must equal
+byte for byte, scrub_helpers' whole-block batch through both, and which path a
+call took, read from the workspace it leaves."""
 import gpu_helpers as H
 import locate_helpers as L
 import scrub_helpers as S
@@ -36,6 +37,14 @@ def position_cases(le, oracle, family):
         yield H.edge_case(le, oracle, family[:4], size, n=k + m + 2)
 
 
+def whole_cases(le, oracle, family):
+    """position_cases' sizes with the k + m + 1 objects of scrub_helpers'
+    whole-block batch."""
+    cls, k, m, w, B = family
+    for size in sizes(family):
+        yield H.edge_case(le, oracle, family[:4], size, n=k + m + 1)
+
+
 def dense_batch(case):
     """(damage list, locate words): object o has block o mod (k + m) damaged
     (scrub_helpers' 64 values at block_hits' places); a data block wholly past
@@ -49,12 +58,13 @@ def dense_batch(case):
     return dmg, words
 
 
-def run_scrub(gpu, le, case, work, par, buffers=None):
+def run_scrub(gpu, le, case, work, par, buffers=None, keep=None):
     """One device.scrub over the given arenas.  report lies in a pre-filled
     [n + 2] tensor (words 1..n covered), totals in a [4] tensor (words 1..2),
     the workspace in WS_FILL bytes with WS_TAIL more behind the query's size.
     Returns (the [n + 2] report tensor, its n covered words, the two totals,
-    errors): the sentinel words and the workspace's tail intact."""
+    errors): the sentinel words and the workspace's tail intact.  `keep`: a
+    list the workspace tensor is appended to, as the call leaves it (path)."""
     n, g = case.n, case.guard
     report = gpu.full((n + 2,), L.PREFILL, dtype=gpu.int32, device="cuda")
     report[0], report[n + 1] = L.SENTINELS
@@ -76,10 +86,31 @@ def run_scrub(gpu, le, case, work, par, buffers=None):
         errors.append(f"{ctx}: totals sentinels {tot[0]:#x}, {tot[3]:#x}")
     if not bool((ws[need:] == WS_FILL).all()):
         errors.append(f"{ctx}: workspace written past its {need} bytes")
+    if keep is not None:
+        keep.append(ws)
     return report, got[1:-1], tot[1:3], errors
 
 
-def check_scrub(gpu, le, case, work, par, want, skip=None):
+def path(gpu, ws, words):
+    """Which path a call took, from the workspace it leaves (scrub.hip): "list"
+    when header word 0 is the number of objects whose word in `words` (the
+    report, or what it must be) names a block and the index words before it
+    are a permutation of those objects
+    (scrub_finish's list, which only the rebuild kernel reads), "composed" when
+    the header is as it was filled and the index words are leoec_heal_dev's
+    `unhealed`, anything else as a description."""
+    n = len(words)
+    left = _u32(ws[:16 + 4 * n].view(gpu.int32))
+    count, index = left[0], left[4:4 + n]
+    named = [o for o, x in enumerate(words) if x not in (0, MANY)]
+    if count == len(named) and sorted(index[:count]) == named:
+        return "list"
+    if count == int.from_bytes(bytes([WS_FILL]) * 4, "little"):
+        return "composed"
+    return f"header word {count:#x}, index words {index[:16]}"
+
+
+def check_scrub(gpu, le, case, work, par, want, skip=None, keep=None):
     """run_scrub of arenas damaged from the case's snapshots, against the
     by-construction words `want`: report == want, totals == (single-bit words,
     MANY words), every object whose word names a block back to the snapshot
@@ -90,7 +121,7 @@ def check_scrub(gpu, le, case, work, par, want, skip=None):
     n, g = case.n, case.guard
     snap, par_snap = case.dev(gpu)
     before, par_before = work.clone(), par.clone()
-    report, got, tot, errors = run_scrub(gpu, le, case, work, par)
+    report, got, tot, errors = run_scrub(gpu, le, case, work, par, keep=keep)
     ctx = f"scrub {case.ident()} bs {case.bs}"
     expect = list(want)
     if skip is not None:
@@ -123,12 +154,14 @@ def locate_then_heal(gpu, le, case, work, par):
     return _u32(lost)
 
 
-def check_equivalence(gpu, le, case, dmg):
+def check_equivalence(gpu, le, case, dmg, arenas=None):
     """The damaged arenas twice: one through device.scrub, one through
     device.locate + device.heal.  Both arenas byte for byte and lost == report,
-    no object left out.  Returns (scrub's arenas, its report words, errors)."""
+    no object left out.  The arenas are damaged_arenas' of the list `dmg`, or
+    (dmg None) the pair `arenas`, damaged by the caller and taken over.
+    Returns (scrub's arenas, its report words, errors)."""
     n, g = case.n, case.guard
-    work, par = L.damaged_arenas(gpu, case, dmg)
+    work, par = L.damaged_arenas(gpu, case, dmg) if dmg is not None else arenas
     work2, par2 = work.clone(), par.clone()
     _, got, tot, errors = run_scrub(gpu, le, case, work, par)
     lost = locate_then_heal(gpu, le, case, work2, par2)
@@ -140,3 +173,26 @@ def check_equivalence(gpu, le, case, dmg):
         if err:
             errors.append(err)
     return work, par, got, errors
+
+
+def check_whole(gpu, le, case, blocks):
+    """scrub_helpers' whole-block damage of `blocks` through one device.scrub
+    (check_scrub: the by-construction report and totals, every byte back to
+    the snapshot) and once more beside device.locate + device.heal
+    (check_equivalence), whose arenas are compared with the snapshot as well.
+    Returns (the first call's path, the errors)."""
+    want = S.whole_words(case, blocks)
+    keep = []
+    work, par = S.whole_arenas(gpu, case, blocks)
+    errors = ["whole blocks: " + e for e in check_scrub(gpu, le, case, work, par, want, keep=keep)[1]]
+    work, par, got, errs = check_equivalence(gpu, le, case, None, S.whole_arenas(gpu, case, blocks))
+    errors += ["whole blocks: " + e for e in errs]
+    snap, par_snap = case.dev(gpu)
+    ctx = f"whole blocks: scrub beside locate + heal {case.ident()} bs {case.bs}"
+    if got != want:
+        errors.append(f"{ctx}: report {_hex(got)}, expected {_hex(want)}")
+    for err in (H.arena_diff(gpu, work, snap, case.guard, f"{ctx}: objs"),
+                H.arena_diff(gpu, par, par_snap, 1, f"{ctx}: parity")):
+        if err:
+            errors.append(err)
+    return path(gpu, keep[0], want), errors

@@ -5,7 +5,10 @@ block of one object, the words leoec_verify_dev, leoec_locate_dev and
 leoec_locate_ws_dev must answer for it by construction, the same words from
 the oracle and the host models (locate_helpers, locate_ws_helpers), and one
 device call each of verify, locate and heal over given arenas with every byte
-and the words around the covered ones compared afterwards."""
+and the words around the covered ones compared afterwards; and the whole-block
+batch of the scrub tests (test_device_scrub.py, test_device_scrub_ws.py, the
+forms modules and the instance children), in which every valid byte of the
+damaged block is wrong."""
 import numpy as np
 
 import gpu_helpers as H
@@ -119,11 +122,12 @@ def damaged_objects(case, dmg, objects=None):
     return out
 
 
-def oracle_flags(oracle, case, dmg):
-    """leoec_verify_dev's words from the oracle: the damaged data re-encoded,
-    bit i set where coding block i differs from the stored one."""
+def flags_of(oracle, case, objs):
+    """leoec_verify_dev's words from the oracle for damaged objects
+    ({o: (data bytes, [m coding blocks])}, damaged_objects' or whole_objects'):
+    the damaged data re-encoded, bit i set where coding block i differs from
+    the stored one; an object not among them is 0."""
     k, m, w = case.params
-    objs = damaged_objects(case, dmg)
     flags = [0] * case.n
     for o, (data, stored) in objs.items():
         ref = oracle.encode(case.cls, k, m, w, data.tobytes())
@@ -131,12 +135,17 @@ def oracle_flags(oracle, case, dmg):
     return flags
 
 
-def model_words(oracle, le, case, dmg, objects=None):
+def oracle_flags(oracle, case, dmg):
+    """flags_of under a damage list."""
+    return flags_of(oracle, case, damaged_objects(case, dmg))
+
+
+def words_of(oracle, le, case, objs, objects=None):
     """The host model's locate words (locate_helpers.model_word, or
-    locate_ws_helpers' for the bitmatrix classes) of `objects` (default: all),
-    as {o: word}; an untouched object is 0."""
+    locate_ws_helpers' for the bitmatrix classes) of `objects` (default: all)
+    for damaged objects ({o: (data bytes, [m coding blocks])}), as {o: word};
+    an object not among them is 0."""
     cfg = (case.cls,) + tuple(case.params)
-    objs = damaged_objects(case, dmg, objects)
     if bitsliced(case.cls):
         T = le.device.locate_bitrows(case.cls, case.params)
         word = lambda data, stored: W.model_word(oracle, cfg, data, stored, T)  # noqa: E731
@@ -145,6 +154,11 @@ def model_words(oracle, le, case, dmg, objects=None):
         word = lambda data, stored: L.model_word(oracle, cfg, case.size, data, stored, T)  # noqa: E731
     wanted = range(case.n) if objects is None else objects
     return {o: word(*objs[o]) if o in objs else 0 for o in wanted}
+
+
+def model_words(oracle, le, case, dmg, objects=None):
+    """words_of under a damage list."""
+    return words_of(oracle, le, case, damaged_objects(case, dmg, objects), objects)
 
 
 def two_block_word(oracle, le, case, dmg, locate):
@@ -163,6 +177,88 @@ def two_block_word(oracle, le, case, dmg, locate):
 
 def _hex(words):
     return [hex(x) for x in words]
+
+
+# ---------------------------------------------------------------------------
+# Whole-block damage.  block_hits damages at most 64 bytes of a block, so after
+# a rebuild every other byte of it equals the snapshot whether the kernel wrote
+# it or not.  Here every valid byte of the block is damaged: a rebuild is right
+# only if it stores every tile, every lane and the ragged tail.
+
+WHOLE_SEED = 0x5C2B
+
+
+def whole_batch(case):
+    """The damaged block of each object of a case of k + m + 1 objects: object
+    b < k + m has block b damaged, object k + m (None) is clean."""
+    assert case.n == case.k + case.m + 1
+    return list(range(case.k + case.m)) + [None]
+
+
+def whole_dense_batch(case):
+    """Any number of objects: object o has block o mod (k + m) damaged."""
+    return [o % (case.k + case.m) for o in range(case.n)]
+
+
+def whole_words(case, blocks):
+    """The locate words the damage means: 1 << b, or 0 for a clean object and
+    for a data block that lies wholly past `size` (no byte to damage)."""
+    return [1 << b if b is not None and block_valid(case, b) else 0 for b in blocks]
+
+
+def whole_values(case, blocks):
+    """{b: (objects whose block b is damaged, [their number, valid bytes of
+    block b] XOR values in 1..255)}, seeded by the case and b; blocks with no
+    valid byte are left out."""
+    out = {}
+    for b in sorted({b for b in blocks if b is not None}):
+        valid = block_valid(case, b)
+        if not valid:
+            continue
+        objects = [o for o, x in enumerate(blocks) if x == b]
+        rng = np.random.Generator(np.random.PCG64([WHOLE_SEED, case.size, case.k, case.w, b]))
+        out[b] = (objects, rng.integers(1, 256, (len(objects), valid), dtype=np.uint8))
+    return out
+
+
+def whole_span(case, b):
+    """(arena, first byte, end) of block b's valid bytes in an object's row of
+    the objs arena (a data block ends at `size`) or of the parity arena."""
+    k, bs = case.k, case.bs
+    if b < k:
+        return "objs", b * bs, b * bs + block_valid(case, b)
+    return "parity", (b - k) * bs, (b - k + 1) * bs
+
+
+def whole_arenas(gpu, case, blocks):
+    """Clones of the case's arenas with the damage applied, by slice."""
+    g = case.guard
+    snap, par_snap = case.dev(gpu)
+    work, par = snap.clone(), par_snap.clone()
+    for b, (objects, values) in whole_values(case, blocks).items():
+        where, lo, hi = whole_span(case, b)
+        t, first = (work, g) if where == "objs" else (par, 1)
+        rows = gpu.tensor([first + o for o in objects], device="cuda")
+        t[rows, lo:hi] ^= gpu.from_numpy(values).cuda()
+    return work, par
+
+
+def whole_objects(case, blocks):
+    """{o: (data bytes, [m coding blocks])} as the damage leaves the damaged
+    objects (damaged_objects' format), every damaged byte inside valid bytes."""
+    out = {}
+    for b, (objects, values) in whole_values(case, blocks).items():
+        where, lo, hi = whole_span(case, b)
+        assert 0 <= lo < hi <= (case.size if where == "objs" else case.m * case.bs), (case.ident(), b)
+        assert values.shape == (len(objects), hi - lo) and values.min() >= 1
+        for o, x in zip(objects, values):
+            assert o not in out
+            data, stored = out[o] = L.object_blocks(case, o)
+            if where == "objs":
+                data[lo:hi] ^= x
+            else:
+                stored[b - case.k][:] ^= x
+    return out
 
 
 # ---------------------------------------------------------------------------

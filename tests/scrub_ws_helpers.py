@@ -7,6 +7,7 @@ scrub_dev_helpers', unchanged."""
 import gpu_helpers as H
 import locate_helpers as L
 import scrub_dev_helpers as D
+import scrub_helpers as S
 
 MANY = L.MANY
 WS_FILL, WS_TAIL, TOTALS_PREFILL = D.WS_FILL, D.WS_TAIL, D.TOTALS_PREFILL
@@ -25,6 +26,14 @@ def cases(le, oracle, family):
     yield from D.position_cases(le, oracle, family)
     assert k * B in H.edge_sizes(k, w, B)
     yield H.edge_case(le, oracle, family[:4], k * B, n=k + m + 2)
+
+
+def whole_cases(le, oracle, family):
+    """cases' three sizes with the k + m + 1 objects of scrub_helpers'
+    whole-block batch."""
+    cls, k, m, w, B = family
+    for size in D.sizes(family) + [k * B]:
+        yield H.edge_case(le, oracle, family[:4], size, n=k + m + 1)
 
 
 def head(nobj):
@@ -46,12 +55,15 @@ def workspace_bytes(le, case, room=None):
     return need
 
 
-def run_scrub(gpu, le, case, work, par, room=None):
+def run_scrub(gpu, le, case, work, par, room=None, keep=None):
     """scrub_dev_helpers.run_scrub for device.scrub_ws: report in a pre-filled
     [n + 2] tensor (words 1..n covered), totals in a [4] tensor (words 1..2),
     the workspace in WS_FILL bytes with WS_TAIL more behind its size.  Returns
     (the [n + 2] report tensor, its n covered words, the two totals, errors):
-    the sentinel words and the workspace's tail intact."""
+    the sentinel words and the workspace's tail intact.  `keep`: a list the
+    workspace tensor is appended to, as the call leaves it
+    (scrub_dev_helpers.path; with room for fewer objects than the batch the
+    header and the list are the last chunk's)."""
     n, g = case.n, case.guard
     report = gpu.full((n + 2,), L.PREFILL, dtype=gpu.int32, device="cuda")
     report[0], report[n + 1] = L.SENTINELS
@@ -72,10 +84,12 @@ def run_scrub(gpu, le, case, work, par, room=None):
         errors.append(f"{ctx}: totals sentinels {tot[0]:#x}, {tot[3]:#x}")
     if not bool((ws[need:] == WS_FILL).all()):
         errors.append(f"{ctx}: workspace written past its {need} bytes")
+    if keep is not None:
+        keep.append(ws)
     return report, got[1:-1], tot[1:3], errors
 
 
-def check_scrub(gpu, le, case, work, par, want, skip=None, room=None):
+def check_scrub(gpu, le, case, work, par, want, skip=None, room=None, keep=None):
     """scrub_dev_helpers.check_scrub for device.scrub_ws: report == want,
     totals == (single-bit words, MANY words), every object whose word names a
     block back to the snapshot byte for byte, a MANY object as it was damaged,
@@ -85,7 +99,7 @@ def check_scrub(gpu, le, case, work, par, want, skip=None, room=None):
     n, g = case.n, case.guard
     snap, par_snap = case.dev(gpu)
     before, par_before = work.clone(), par.clone()
-    report, got, tot, errors = run_scrub(gpu, le, case, work, par, room)
+    report, got, tot, errors = run_scrub(gpu, le, case, work, par, room, keep)
     ctx = f"scrub_ws {case.ident()} bs {case.bs} room {room}"
     expect = list(want)
     if skip is not None:
@@ -118,13 +132,14 @@ def locate_then_heal(gpu, le, case, work, par):
     return _u32(lost)
 
 
-def check_equivalence(gpu, le, case, dmg, room=None):
+def check_equivalence(gpu, le, case, dmg, room=None, arenas=None):
     """The damaged arenas twice: one through device.scrub_ws, one through
     device.locate_ws + device.heal.  Both arenas byte for byte and lost ==
-    report, no object left out.  Returns (scrub_ws's arenas, its report words,
-    its totals, errors)."""
+    report, no object left out.  The arenas are damaged_arenas' of the list
+    `dmg`, or (dmg None) the pair `arenas`, damaged by the caller and taken
+    over.  Returns (scrub_ws's arenas, its report words, its totals, errors)."""
     g = case.guard
-    work, par = L.damaged_arenas(gpu, case, dmg)
+    work, par = L.damaged_arenas(gpu, case, dmg) if dmg is not None else arenas
     work2, par2 = work.clone(), par.clone()
     _, got, tot, errors = run_scrub(gpu, le, case, work, par, room)
     lost = locate_then_heal(gpu, le, case, work2, par2)
@@ -136,3 +151,27 @@ def check_equivalence(gpu, le, case, dmg, room=None):
         if err:
             errors.append(err)
     return work, par, got, tot, errors
+
+
+def check_whole(gpu, le, case, blocks, room=None):
+    """scrub_dev_helpers.check_whole for device.scrub_ws: scrub_helpers'
+    whole-block damage of `blocks` through one call (the by-construction report
+    and totals, every byte back to the snapshot) and once more beside
+    device.locate_ws + device.heal, whose arenas are compared with the snapshot
+    as well.  Returns (the first call's path, the errors)."""
+    want = S.whole_words(case, blocks)
+    keep = []
+    work, par = S.whole_arenas(gpu, case, blocks)
+    errors = ["whole blocks: " + e
+              for e in check_scrub(gpu, le, case, work, par, want, room=room, keep=keep)[1]]
+    work, par, got, _, errs = check_equivalence(gpu, le, case, None, room, S.whole_arenas(gpu, case, blocks))
+    errors += ["whole blocks: " + e for e in errs]
+    snap, par_snap = case.dev(gpu)
+    ctx = f"whole blocks: scrub_ws beside locate_ws + heal {case.ident()} bs {case.bs} room {room}"
+    if got != want:
+        errors.append(f"{ctx}: report {_hex(got)}, expected {_hex(want)}")
+    for err in (H.arena_diff(gpu, work, snap, case.guard, f"{ctx}: objs"),
+                H.arena_diff(gpu, par, par_snap, 1, f"{ctx}: parity")):
+        if err:
+            errors.append(err)
+    return D.path(gpu, keep[0], want), errors

@@ -10,8 +10,17 @@ a dense batch (object o has block o mod (k + m) damaged), for the six families
 of locate_helpers.FAMILIES (the fused configurations at 256 lanes, the 64-lane
 tiles, K = 16) at the sizes k B - 1 and 16 w (k - 2) + 5.  Expected words are
 by construction (scrub_helpers.position_batch, held against the oracle and the
-host model by test_device_scrub_positions.py's CPU test)."""
+host model by test_device_scrub_positions.py's CPU test).
+
+Those batches damage at most 64 bytes of a block, so every other byte of it
+equals the snapshot whether gf8_heal_list stored it or not.  The whole-block
+batch (scrub_helpers.whole_batch, held against the oracle and the host model by
+test_scrub_whole_cpu.py) damages every valid byte of block b in object b: the
+result is right only if every tile, every lane, both store paths and the ragged
+tail were written.  The dense form of it in a batch of twice the launch's grid
+runs the kernel's loop into its second trip in the product library."""
 import os
+import re
 import subprocess
 import sys
 
@@ -97,6 +106,71 @@ def test_device_scrub_dense_batch(gpu, le, oracle, family):
         errors += D.check_scrub(gpu, le, case, work, par, want)[1]
         errors += D.check_equivalence(gpu, le, case, dmg)[3]
     assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_whole_blocks(gpu, le, oracle, family):
+    """Object b has every valid byte of block b damaged: one scrub, and one
+    beside device.locate + device.heal, both back to the snapshot byte for
+    byte; the rebuild was gf8_heal_list's (the list in the workspace)."""
+    errors = []
+    for case in D.whole_cases(le, oracle, family):
+        path, errs = D.check_whole(gpu, le, case, S.whole_batch(case))
+        errors += errs
+        if path != "list":
+            errors.append(f"{case.ident()}: not the kernel path (more than 16 heal tables in this "
+                          f"process?): {path}")
+    assert not errors, "\n".join(errors[:20])
+
+
+# gf8_heal_list's grid, restated: compute units x resident workgroups
+# (scrub_impl.hpp: 4 SIMDs of kGf8HealWaves waves, wg / 64 waves a workgroup)
+GF8_HEAL_WAVES = 4
+LARGE = ("vandrs", 4, 2, 8, 4224)  # 256 lanes: a full 4,096-byte tile and a 128-byte one
+
+
+def gf8_heal_list_resident(wg):
+    return 4 * GF8_HEAL_WAVES * 64 // wg
+
+
+def test_grid_constants_are_the_sources():
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "leo_erasure_amd", "csrc")
+    with open(os.path.join(csrc, "heal_impl.hpp")) as fh:
+        heal = fh.read()
+    with open(os.path.join(csrc, "scrub_impl.hpp")) as fh:
+        scrub = fh.read()
+    assert re.findall(r"#define LEOEC_GF8_HEAL_WAVES (\d+)", heal) == [str(GF8_HEAL_WAVES)]
+    assert "constexpr int kGf8HealWaves = LEOEC_GF8_HEAL_WAVES;" in heal
+    assert ("inline uint32_t gf8_heal_list_resident(uint32_t wg) "
+            "{ return 4u * (uint32_t)kGf8HealWaves * 64u / wg; }") in scrub
+    assert "uint64_t grid = (uint64_t)device_cus() * gf8_heal_list_resident(wg);" in scrub
+    assert "grid = grid < all ? grid : all;" in scrub
+    assert gf8_heal_list_resident(256) == 4 and gf8_heal_list_resident(64) == 16
+    cls, k, m, w, B = LARGE
+    assert B <= 160 * 1024 and -(-B // 4096) == 2  # the 256-lane form, two tiles a block
+
+
+@pytest.mark.gpu
+def test_device_scrub_batch_larger_than_the_grid(gpu, le, oracle):
+    """The dense whole-block batch with objects x tiles at least twice
+    gf8_heal_list's grid: every workgroup takes a second item
+    (`item += gridDim.x`) in the product library.  Every object against the
+    oracle's snapshot."""
+    cls, k, m, w, B = LARGE
+    cus = gpu.cuda.get_device_properties(gpu.cuda.current_device()).multi_processor_count
+    grid = cus * gf8_heal_list_resident(256)
+    tiles = -(-B // 4096)
+    n = -(-2 * grid // tiles)
+    case = H.EdgeCase(le, oracle, LARGE[:4], k * B - 1, n)
+    assert case.bs == B and n * tiles >= 2 * grid
+    blocks = S.whole_dense_batch(case)
+    want = S.whole_words(case, blocks)
+    assert all(x == 1 << (o % (k + m)) for o, x in enumerate(want))  # no object left out
+    work, par = S.whole_arenas(gpu, case, blocks)
+    keep = []
+    errors = D.check_scrub(gpu, le, case, work, par, want, keep=keep)[1]
+    assert not errors, "\n".join(e[:2000] for e in errors[:20])
+    assert D.path(gpu, keep[0], want) == "list"
 
 
 @pytest.mark.gpu

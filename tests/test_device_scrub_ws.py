@@ -12,10 +12,21 @@ bitmatrix families of locate_ws_helpers.FAMILIES at the sizes k B - 1 and
 16 w (k - 2) + 5 (every packet has whole 1 KiB tiles and a last partial one,
 the last data block is ragged at the first size, empty with the one before it
 ragged at the second) and at k B, where no block is clipped
-(scrub_ws_helpers.cases).  Expected words are by construction."""
+(scrub_ws_helpers.cases).  Expected words are by construction.
+
+Those batches damage at most 64 bytes of a block, 64 / w of a packet, all in
+lane 0's column of one tile: every other byte equals the snapshot whether
+bit_heal_list stored it or not.  The whole-block batch
+(scrub_helpers.whole_batch, held against the oracle and the host model by
+test_scrub_whole_cpu.py) damages every valid byte of block b in object b: the
+result is right only if every tile of every packet, every lane, both store
+paths and the ragged tail were written.  The dense form of it in a batch of
+twice the launch's grid runs the kernel's loop into its second trip in the
+product library."""
 import contextlib
 import ctypes
 import os
+import re
 import subprocess
 import sys
 
@@ -129,6 +140,79 @@ def test_device_scrub_ws_small_workspaces(gpu, le, oracle, family):
                 if err:
                     errors.append(err)
     assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_whole_blocks(gpu, le, oracle, family):
+    """Object b has every valid byte of block b damaged: one scrub_ws, and one
+    beside device.locate_ws + device.heal, both back to the snapshot byte for
+    byte; the rebuild was bit_heal_list's (the list in the workspace).  Then
+    once more with room for one object in the workspace."""
+    errors = []
+    for case in X.whole_cases(le, oracle, family):
+        blocks = S.whole_batch(case)
+        path, errs = X.check_whole(gpu, le, case, blocks)
+        errors += errs
+        if path != "list":
+            errors.append(f"{case.ident()}: not the kernel path (more than 16 block tables in this "
+                          f"process?): {path}")
+        work, par = S.whole_arenas(gpu, case, blocks)
+        errors += ["whole blocks: " + e for e in
+                   X.check_scrub(gpu, le, case, work, par, S.whole_words(case, blocks), room=1)[1]]
+    assert not errors, "\n".join(errors[:20])
+
+
+# bit_heal_list's grid, restated: compute units x resident workgroups
+# (scrub_bit_impl.hpp: one wave each, 32 waves a compute unit, w KiB of its
+# 160 KiB of LDS each)
+# (m = 3: neither side builds an m = 2 Cauchy matrix past w = 20)
+LARGE = ("cauchyrs", 2, 3, 32, 1040 * 32)  # packets of 1,040 bytes: a full tile and a 16-byte one
+
+
+def bit_heal_list_resident(w):
+    return min(160 // w, 32)
+
+
+def test_grid_constants_are_the_sources(le, oracle):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "leo_erasure_amd", "csrc", "scrub_bit_impl.hpp")) as fh:
+        text = fh.read()
+    assert re.findall(r"constexpr int kBitHealLanes = (\d+);", text) == ["64"]
+    assert "constexpr uint32_t kBitHealTile = kBitHealLanes * 16u;" in text and X.TILE == 64 * 16
+    assert re.search(r"inline uint32_t bit_heal_list_resident\(uint32_t w\) \{\s*"
+                     r"const uint32_t by_lds = 160u / w;[^\n]*\n\s*"
+                     r"return by_lds < 32u \? by_lds : 32u;\s*\}", text)
+    assert "uint64_t grid = (uint64_t)device_cus() * bit_heal_list_resident(a.w);" in text
+    assert "grid = grid < all ? grid : all;" in text
+    assert [bit_heal_list_resident(w) for w in (2, 5, 6, 17, 32)] == [32, 32, 26, 9, 5]
+    cls, k, m, w, B = LARGE
+    assert B % (16 * w) == 0 and -(-(B // w) // X.TILE) == 2 and W.served(cls, k, m, w)
+    assert len(oracle.encode(cls, k, m, w, b"\x5a")) == k + m
+    assert le.device.scrub_ws_workspace(cls, (k, m, w), k * B - 1, 1) == 32 + m * B
+
+
+@pytest.mark.gpu
+def test_device_scrub_ws_batch_larger_than_the_grid(gpu, le, oracle):
+    """The dense whole-block batch with objects x tiles at least twice
+    bit_heal_list's grid: every workgroup takes a second item
+    (`item += gridDim.x`) in the product library, at w = 32 (5 resident
+    workgroups a compute unit, 32 KiB of LDS each).  Every object against the
+    oracle's snapshot."""
+    cls, k, m, w, B = LARGE
+    cus = gpu.cuda.get_device_properties(gpu.cuda.current_device()).multi_processor_count
+    grid = cus * bit_heal_list_resident(w)
+    tiles = -(-(B // w) // X.TILE)
+    n = -(-2 * grid // tiles)
+    case = H.EdgeCase(le, oracle, LARGE[:4], k * B - 1, n)
+    assert case.bs == B and n * tiles >= 2 * grid
+    blocks = S.whole_dense_batch(case)
+    want = S.whole_words(case, blocks)
+    assert all(x == 1 << (o % (k + m)) for o, x in enumerate(want))  # no object left out
+    work, par = S.whole_arenas(gpu, case, blocks)
+    keep = []
+    errors = X.check_scrub(gpu, le, case, work, par, want, keep=keep)[1]
+    assert not errors, "\n".join(e[:2000] for e in errors[:20])
+    assert D.path(gpu, keep[0], want) == "list"
 
 
 @pytest.mark.gpu

@@ -31,7 +31,12 @@ tests/gf8_heal_instances_child.py heals exactly 16 configurations, one per K,
 in a process of its own; test_gf8_heal_every_k_in_own_process starts it twice
 (test_heal_cpu.py::test_heal_rows_every_fused_configuration pins the table
 contents of the configurations neither child launches).  The 64-lane form
-stays with the families that cover it: the instance is the same."""
+stays with the families that cover it: the instance is the same.
+
+gf8_heal_list<K> (leoec_scrub_dev's rebuild) depends on the same 16 tables:
+tests/scrub_instances_child.py scrubs one configuration per K, m = 2..4, in a
+process of its own, with scrub_helpers' whole-block batch and its position
+batch, and reads from the workspace that the kernel path ran."""
 import os
 import subprocess
 import sys
@@ -39,6 +44,7 @@ import sys
 import pytest
 
 import gf8_heal_instances_child as C
+import scrub_instances_child as SC
 import gpu_helpers as H
 import locate_helpers as L
 import scrub_helpers as S
@@ -207,3 +213,41 @@ def test_gf8_heal_every_k_in_own_process(gpu, tmp_path):
             tail = fh.read()[-4000:]
         assert rc == 0, f"heal instances, group {name}, failed (rc {rc}), {log}:\n{tail}"
         assert f"group {name}: 16 configurations healed" in tail, tail
+
+
+def test_scrub_child_configurations(le):
+    """No GPU: the scrub child has one configuration per K = 1..16, m cycling
+    over 2..4 (scrub needs m >= 2), the classes alternating; every one is
+    served; its sizes are this module's and have no empty data block."""
+    assert len(SC.CONFIGS) == 16 == SC.MAX_TABLES == C.MAX_TABLES
+    assert [k for _, k, _ in SC.CONFIGS] == list(range(1, 17))
+    assert [m for _, _, m in SC.CONFIGS] == [2, 3, 4] * 5 + [2]
+    assert [cls for cls, _, _ in SC.CONFIGS] == ["vandrs", "isars"] * 8
+    for cls, k, m in SC.CONFIGS:
+        assert L.served(cls, k, m, 8)
+        assert le.device.scrub_workspace(cls, (k, m, 8), SC.sizes(k)[0], k + m + 2) == \
+            16 + (4 * (k + m + 2) + 15) // 16 * 16
+        assert SC.sizes(k) == sizes(k)
+        for size, bs, last in zip(sizes(k), (4224, 128), (4221, 5)):
+            assert le.layout(cls, (k, m, 8), size)[0] == bs
+            assert H.block_valids(k, bs, size) == [bs] * (k - 1) + [last]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_gf8_heal_list_every_k_in_own_process(gpu, tmp_path):
+    """gf8_heal_list<K> for every K, 16 configurations in one fresh process
+    (the table cache's bound).  The child's output goes to a log in the test's
+    temporary directory; a failure shows its tail."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, LIBC_FATAL_STDERR_="1")
+    env.pop("LEOEC_LIBRARY", None)
+    log = str(tmp_path / "gf8_heal_list.log")
+    cmd = [sys.executable, "-u", os.path.abspath(SC.__file__)]
+    with open(log, "w") as fh:
+        rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=130)
+    with open(log) as fh:
+        text = fh.read()
+    assert rc == 0, f"scrub instances failed (rc {rc}), {log}:\n{text[-4000:]}"
+    assert "16 configurations scrubbed" in text, text[-4000:]
+    assert text.count(" 0 errors") == 32, text[-4000:]  # one line per configuration and size

@@ -33,9 +33,14 @@ short) and 16 w (k - 1) + 5 (16 w-byte blocks, the last one 5 bytes), 3
 objects each.
 
 The second half holds the scrub calls (verify, locate_ws, heal) at the limits
-bit_locate is written against, with scrub_helpers' position batch."""
+bit_locate is written against, with scrub_helpers' position batch, and the
+sweep of bit_heal_list (leoec_scrub_ws_dev's rebuild: one instance, w, k and m
+runtime values) over every w and the same limits, in child processes of at
+most 16 configurations (tests/scrub_ws_instances_child.py)."""
 import glob
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -45,6 +50,7 @@ import instance_tables as T
 import locate_helpers as L
 import locate_ws_helpers as W
 import scrub_helpers as S
+import scrub_ws_instances_child as BC
 import test_code_objects as CO
 
 E_UNSUPPORTED = -14
@@ -435,3 +441,96 @@ def test_scrub_at_locate_ws_limits(gpu, le, oracle, row):
         again = [0] * (case.n - 1) + [want[-1]]
         errors += S.check_locate(gpu, le, case, work, par, again, skip)[1]
     assert not errors, "\n".join(errors[:20])
+
+
+# ---------------------------------------------------------------------------
+# bit_heal_list over its runtime parameters (scrub_ws_instances_child.py).
+
+def test_bit_heal_list_sweep_is_what_it_claims(le, oracle):
+    """No GPU: the groups hold every cauchyrs w = 2..32, the ten liberation
+    widths, the limits and k = 1, each configuration once, at most 16 a group;
+    every one is served by leoec_scrub_ws_dev (locate_ws_helpers.served and
+    k + m <= 31), accepted by the oracle, and of the stated geometry."""
+    cfgs = BC.configs()
+    assert len(cfgs) == len(set(cfgs)) == 45
+    assert sorted(c for g in BC.GROUPS.values() for c in g) == sorted(cfgs)
+    assert all(len(g) == 15 <= BC.MAX_TABLES for g in BC.GROUPS.values())
+    assert BC.MAX_WORDS == W.MAX_WORDS
+    assert sorted({w for cls, _, _, w in cfgs if cls == "cauchyrs"}) == list(range(2, 33))
+    assert sorted({w for cls, _, _, w in cfgs if cls == "liberation"}) == list(BC.LIB_WS)
+    assert all(c in cfgs for c in BC.LIMITS + BC.ONES)
+    assert BC.LIMITS == [("cauchyrs", 27, 4, 8), ("cauchyrs", 29, 2, 8), ("cauchyrs", 12, 3, 32),
+                         ("cauchyrs", 6, 4, 32), ("liberation", 24, 2, 31)]
+    assert BC.ONES == [("cauchyrs", 1, 2, 8), ("liberation", 1, 2, 3)]
+    # the sweep's m: 2, 3 and 4 all met below w = 17, 3 and 4 above
+    sweep = [BC.cauchy_config(w) for w in range(2, 33)]
+    assert {m for _, _, m, w in sweep if w <= 16} == {2, 3, 4}
+    assert {m for _, _, m, w in sweep if w > 16} == {3, 4}
+    # what the limits sit on
+    assert (27 + 4, 29 + 2, 2 * 12 * 32, 3 * 6 * 32, 24 * 31) == (31, 31, 768, 576, 744)
+    assert (29 + 3) // 4 == 8  # 29 survivor ids: all 8 id words of a record
+    cid = le._lib.CODING_IDS
+    for cfg in cfgs:
+        cls, k, m, w = cfg
+        assert W.served(*cfg) and k + m <= 31 and m >= 2, cfg
+        assert cls == "liberation" or k + m <= 1 << w, cfg
+        assert oracle.check_params(*cfg) == 0 and le.lib.leoec_check_params(cid[cls], k, m, w) == 0, cfg
+        assert len(oracle.encode(cls, k, m, w, b"\x5a")) == k + m
+        szs = BC.sizes(cfg)
+        assert len(szs) == (2 if k >= 2 else 1)
+        n = k + m + 2
+        B = BC.PACKET * w
+        assert le.layout(cls, (k, m, w), szs[0])[0] == B
+        assert H.block_valids(k, B, szs[0]) == [B] * (k - 1) + [B - 1]
+        # a whole 1 KiB tile and a 16-byte one
+        assert BC.PACKET // 1024 == 1 and BC.PACKET % 1024 == 16
+        assert le.device.scrub_ws_workspace(cls, (k, m, w), szs[0], n) == \
+            16 + (4 * n + 15) // 16 * 16 + n * m * B
+        if k >= 2:
+            assert le.layout(cls, (k, m, w), szs[1])[0] == 16 * w  # packets of 16 bytes: one lane of 64
+            assert H.block_valids(k, 16 * w, szs[1]) == [16 * w] * (k - 1) + [5]
+
+
+@pytest.mark.parametrize("name", sorted(BC.GROUPS))
+def test_bit_heal_list_sweep_against_oracle_and_model(le, oracle, name):
+    """No GPU: at both sizes of every configuration the whole-block damage
+    lies inside valid bytes, no object but the clean one expects 0, the
+    oracle's re-encoding gives the by-construction flags and
+    locate_ws_helpers.model_word the by-construction words."""
+    for cfg, size in [(cfg, size) for cfg in BC.GROUPS[name] for size in BC.sizes(cfg)]:
+        cls, k, m, w = cfg
+        case = H.EdgeCase(le, oracle, cfg, size, k + m + 1)
+        blocks = S.whole_batch(case)
+        words = S.whole_words(case, blocks)
+        assert words == [1 << b for b in range(k + m)] + [0], cfg
+        objs = S.whole_objects(case, blocks)
+        assert sorted(objs) == list(range(k + m))
+        flags = [(1 << m) - 1] * k + [1 << i for i in range(m)] + [0]
+        assert S.flags_of(oracle, case, objs) == flags, cfg
+        model = S.words_of(oracle, le, case, objs)
+        assert [model[o] for o in range(case.n)] == words, cfg
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_bit_heal_list_sweep_in_own_processes(gpu, tmp_path):
+    """bit_heal_list at every configuration of the sweep, one group of at most
+    16 per fresh process (the block table cache's bound); the first child that
+    fails or dies ends the test and nothing is started after it.  The child's
+    output goes to a log in the test's temporary directory; a failure shows
+    its tail."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, LIBC_FATAL_STDERR_="1")
+    env.pop("LEOEC_LIBRARY", None)
+    for name in sorted(BC.GROUPS):
+        log = str(tmp_path / f"bit_heal_list_{name}.log")
+        cmd = [sys.executable, "-u", os.path.abspath(BC.__file__), name]
+        with open(log, "w") as fh:
+            rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT,
+                                 timeout=90)
+        with open(log) as fh:
+            text = fh.read()
+        assert rc == 0, f"bit_heal_list sweep, group {name}, failed (rc {rc}), {log}:\n{text[-4000:]}"
+        assert f"group {name}: {len(BC.GROUPS[name])} configurations scrubbed" in text, text[-4000:]
+        lines = sum(len(BC.sizes(cfg)) for cfg in BC.GROUPS[name])
+        assert text.count(" 0 errors") == lines, text[-4000:]

@@ -69,6 +69,12 @@ def test_scrub_grid_caps(gpu, le, oracle, family, measure):
             work, par = L.damaged_arenas(gpu, case, dmg)
             errors += [f"LEOEC_SCRUB_GRID={grid} dense: {e}"
                        for e in D.check_scrub(gpu, le, case, work, par, want)[1]]
+        # every valid byte of block b damaged in object b: every item's stores are needed
+        for case in D.whole_cases(le, oracle, family):
+            blocks = S.whole_batch(case)
+            work, par = S.whole_arenas(gpu, case, blocks)
+            errors += [f"LEOEC_SCRUB_GRID={grid} whole blocks: {e}" for e in
+                       D.check_scrub(gpu, le, case, work, par, S.whole_words(case, blocks))[1]]
     assert not errors, "\n".join(errors[:20])
 
 
