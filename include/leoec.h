@@ -302,6 +302,58 @@ int leoec_locate_ws_dev(int coding, int k, int m, int w, const uint8_t *objs, ui
                         uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
                         uint32_t *lost, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* Workspace bytes leoec_locate_gfw_dev wants for this batch: for everything
+ * leoec_locate_ws_dev serves, that call's query (same value, same statuses);
+ * for class (c) below nobj * m * block_size (one pass); LEOEC_E_BAD_SIZE when
+ * that overflows; bytes == NULL: LEOEC_E_ARG, checked after the served checks.
+ * Configurations leoec_locate_gfw_dev does not serve, and invalid ones, get
+ * its statuses.  Needs no device. */
+int leoec_locate_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                   uint64_t *bytes);
+
+/* leoec_locate_ws_dev plus the GF(2^w) word classes, in the relation
+ * leoec_locate_ws_dev has to leoec_locate_dev.  Words, layout, alignment,
+ * stride rules and the reading of bytes past `size` are leoec_locate_ws_dev's:
+ * every word of lost is overwritten with 0, one bit b < k + m or
+ * LEOEC_LOCATE_MANY, and the words go into leoec_heal_dev as they are; objs
+ * and parity are never written.  The workspace's contents after the call are
+ * unspecified.
+ * Served:
+ *   (a) everything leoec_locate_ws_dev serves (its classes (a) and (b)): the
+ *       call and the query are forwarded to it, with the same statuses,
+ *       workspace size and words;
+ *   (c) vandrs w = 16 / 32, and vandrs / isars w = 8 with k > 16 or m > 4, all
+ *       with m >= 2 and k + m <= 32 (one bit of the word per block).
+ * Everything else (m = 1, k + m > 32, the bitmatrix configurations
+ * leoec_locate_ws_dev refuses) is LEOEC_E_UNSUPPORTED, returned before the
+ * device is opened; invalid parameters keep their leoec_check_params status;
+ * nobj == 0 is LEOEC_OK with nothing written.  The checks come in
+ * leoec_locate_ws_dev's order: layout and parameters, served, empty batch,
+ * pointers and strides, workspace, then the device.
+ * workspace for (c): device, 16-byte aligned, at least m * block_size bytes
+ * (one object), else LEOEC_E_ARG; a smaller workspace than the query's gives
+ * the same words in more chunks of objects on the same stream.
+ * How (c) tells: a block is a row of little-endian w-bit words.  Per word
+ * column the syndromes s_i = stored coding block i ^ encoding of the data are
+ * all zero (clean), non-zero in one i only (coding block i), or
+ * s_i = C[i][j] / C[0][j] * s_0 in GF(2^w) for every i (data block j); an
+ * object's answer is the block that fits every column.  That is unique
+ * because no entry and no 2 x 2 minor of the coding matrix C is zero, which
+ * is checked when the code's table is built (leoec_locate_wrows).
+ * The limit at m = 2 is leoec_locate_dev's: two damaged blocks may be reported
+ * as a third.  At k + m = 32 the bit of the last coding block (id 31) is
+ * LEOEC_LOCATE_MANY's own, the limit leoec_locate_ws_dev documents: that word
+ * says either, and leoec_heal_dev reads it as block 31.
+ * For (c) the call allocates nothing, uploads nothing and never synchronises:
+ * per chunk the class's encode into the workspace, a memset and two launches
+ * on `stream`, so it can be captured into a graph, after the first call: the
+ * first call of a code builds its ratio table on the host (kept for the
+ * process's life, under 1 KB) and the first call on a device loads this
+ * call's code object (1-2 ms); the leoec_gf_init warm-up covers neither. */
+int leoec_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t *objs, uint64_t obj_stride,
+                         uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
+                         uint32_t *lost, void *workspace, uint64_t workspace_bytes, void *stream);
+
 /* Workspace bytes leoec_scrub_dev needs for nobj objects:
  * 16 + round_up(4 * nobj, 16), a header and one index word per object;
  * LEOEC_E_BAD_SIZE when that overflows; bytes == NULL: LEOEC_E_ARG.
@@ -465,6 +517,17 @@ int leoec_locate_bitrows(int coding, int k, int m, int w, uint32_t *rows, int ca
  * uniqueness rests on are checked (no zero entry, no singular 2 x 2 minor of
  * C): LEOEC_E_UNSUPPORTED if either fails. */
 int leoec_locate_rows(int coding, int k, int m, int w, uint32_t *ratio, int cap);
+
+/* The ratios leoec_locate_gfw_dev tests the syndromes of its class (c) with;
+ * needs no device.  ratio (cap >= (m-1) * k words): word (i-1) * k + j is
+ * T[i][j] = C[i][j] / C[0][j] in GF(2^w), i = 1..m-1, C being
+ * leoec_coding_matrix's.  ratio == NULL or cap too small: LEOEC_E_ARG.  Serves
+ * class (c) of leoec_locate_gfw_dev only and gives its statuses otherwise;
+ * class (a) is LEOEC_E_UNSUPPORTED (those tables are leoec_locate_rows and
+ * leoec_locate_bitrows).  While building T the two properties the answer's
+ * uniqueness rests on are checked (no zero entry, no singular 2 x 2 minor of
+ * C): LEOEC_E_UNSUPPORTED if either fails. */
+int leoec_locate_wrows(int coding, int k, int m, int w, uint32_t *ratio, int cap);
 
 /* The map leoec_heal_dev uses for one mask of lost ids; needs no device.
  * surv[0..k): the survivor ids; want[0..*nwant): the lost ids ascending;

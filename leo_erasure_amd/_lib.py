@@ -46,6 +46,7 @@ EXPORTS = (
     "leoec_heal_rows", "leoec_locate_dev", "leoec_locate_rows", "leoec_locate_ws_dev_workspace",
     "leoec_locate_ws_dev", "leoec_locate_bitrows", "leoec_scrub_dev_workspace", "leoec_scrub_dev",
     "leoec_scrub_ws_dev_workspace", "leoec_scrub_ws_dev", "leoec_scrub_bitrows",
+    "leoec_locate_gfw_dev_workspace", "leoec_locate_gfw_dev", "leoec_locate_wrows",
 )
 
 
@@ -106,6 +107,9 @@ def _load(path=LIB_PATH):
     L.leoec_locate_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
     L.leoec_locate_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
     L.leoec_locate_bitrows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
+    L.leoec_locate_gfw_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
+    L.leoec_locate_gfw_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
+    L.leoec_locate_wrows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
     L.leoec_scrub_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
     L.leoec_scrub_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
     L.leoec_scrub_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]

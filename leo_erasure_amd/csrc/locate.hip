@@ -20,19 +20,28 @@
 //                   packet form of the test (locate_bitrows.hpp);
 //   locate_finish.
 // Everything leoec_locate_dev serves is forwarded to it.
+// leoec_locate_gfw_dev adds the GF(2^w) word classes in the same way (vandrs
+// w = 16 / 32; vandrs / isars w = 8 with k > 16 or m > 4): the same four
+// steps with gfw_locate (locate_gfw_impl.hpp) in bit_locate's place, the word
+// form of the test (locate_wrows.hpp).  Everything leoec_locate_ws_dev serves
+// is forwarded to it.
 // leoec_scrub_dev (scrub.hip) runs op_locate_dev with its own steps in it
 // (scrub_steps.hpp): its kernel stands in locate_finish's place;
 // leoec_scrub_ws_dev does the same with op_locate_ws_dev's bitmatrix branch.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
+#include <map>
+#include <mutex>
 #include <utility>
 #include <vector>
 
 #include "engine.hpp"
 #include "locate_bitrows.hpp"
+#include "locate_gfw_impl.hpp"
 #include "locate_impl.hpp"
 #include "locate_rows.hpp"
+#include "locate_wrows.hpp"
 #include "scrub_steps.hpp"
 
 namespace leoec {
@@ -352,9 +361,184 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
   return LEOEC_OK;
 }
 
+namespace {
+
+// ---------------------------------------------------------------------------
+// The GF(2^w) word classes: leoec_locate_gfw_dev.
+
+// What neither leoec_locate_dev nor leoec_locate_ws_dev serves of the matrix
+// classes, with a second coding block and a bit for every block.
+bool gfw_locate_served(int coding, int k, int m, int w) {
+  return (coding == LEOEC_VANDRS || coding == LEOEC_ISARS) && (w == 8 || w == 16 || w == 32) &&
+         !locate_served(coding, k, m, w) && m >= 2 && k + m <= 32;
+}
+
+// The ratio table of a code, built once and kept with the cached Code (get_code
+// never frees one): at (16,16,32) the build is 240 divisions and 28,800
+// products bit by bit, milliseconds, which a call's host time would show.
+int gfw_ratio(const Code* c, const std::vector<uint32_t>** out) {
+  struct Entry {
+    int rc;
+    std::vector<uint32_t> ratio;
+  };
+  static std::mutex mu;
+  static std::map<const Code*, Entry> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(c);
+  if (it == cache.end()) {
+    Entry e;
+    e.rc = locate_build_wrows(c->C.a.data(), c->k, c->m, c->w, &e.ratio);
+    it = cache.emplace(c, std::move(e)).first;
+  }
+  *out = &it->second.ratio;
+  return it->second.rc;
+}
+
+// The code and its ratio table; needs no device.
+int gfw_locate_code(int coding, int k, int m, int w, const Code** c,
+                    const std::vector<uint32_t>** ratio) {
+  int rc = check_params(coding, k, m, w);
+  if (rc) return rc;
+  if (!gfw_locate_served(coding, k, m, w)) return LEOEC_E_UNSUPPORTED;
+  if ((rc = get_code(coding, k, m, w, c))) return rc;
+  if ((*c)->bitmatrix || (*c)->C.a.size() != (size_t)m * k) return LEOEC_E_UNSUPPORTED;
+  return gfw_ratio(*c, ratio);
+}
+
+// Class (a) of leoec_locate_gfw_dev: what leoec_locate_ws_dev serves, and the
+// bitmatrix configurations it refuses, which stay refused.
+bool gfw_forwarded(int coding, int k, int m, int w) {
+  return bit_class(coding) || locate_served(coding, k, m, w);
+}
+
+int op_locate_wrows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
+  int rc = check_params(coding, k, m, w);
+  if (rc) return rc;
+  if (gfw_forwarded(coding, k, m, w)) return LEOEC_E_UNSUPPORTED;
+  const Code* c;
+  const std::vector<uint32_t>* t;
+  if ((rc = gfw_locate_code(coding, k, m, w, &c, &t))) return rc;
+  if (!ratio || cap < (m - 1) * k) return LEOEC_E_ARG;
+  for (size_t i = 0; i < t->size(); ++i) ratio[i] = (*t)[i];
+  return LEOEC_OK;
+}
+
+int op_locate_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                uint64_t* bytes) {
+  uint64_t bs;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if (gfw_forwarded(coding, k, m, w))
+    return op_locate_ws_dev_workspace(coding, k, m, w, size, nobj, bytes);
+  const Code* c;
+  const std::vector<uint32_t>* t;
+  if ((rc = gfw_locate_code(coding, k, m, w, &c, &t))) return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  uint64_t per, all;
+  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
+    return LEOEC_E_BAD_SIZE;
+  *bytes = all;
+  return LEOEC_OK;
+}
+
+int launch_gfw_locate(int w, const GfwLocArgs& a, uint64_t no, uint32_t* lost, hipStream_t s) {
+  const dim3 grid((uint32_t)(no * a.tiles)), block(kGfwLocLanes);
+  if (w == 8) return launch_kernel(gfw_locate<8>, grid, block, 0, s, a, lost);
+  if (w == 16) return launch_kernel(gfw_locate<16>, grid, block, 0, s, a, lost);
+  return launch_kernel(gfw_locate<32>, grid, block, 0, s, a, lost);
+}
+
+int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                      uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                      uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+  uint64_t bs;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if (gfw_forwarded(coding, k, m, w))
+    return op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+                            lost, workspace, workspace_bytes, s, nullptr);
+  const Code* c;
+  const std::vector<uint32_t>* ratio;
+  if ((rc = gfw_locate_code(coding, k, m, w, &c, &ratio))) return rc;
+  if (nobj == 0 || bs == 0) return LEOEC_OK;
+  if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
+  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
+  if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per) return LEOEC_E_ARG;
+  if (ratio->size() > (size_t)kGfwLocWords) return LEOEC_E_UNSUPPORTED;  // (k + m <= 32: never)
+  if ((rc = device_init())) return rc;
+  std::vector<Shard> in(k);
+  std::vector<int> surv(k), want(m);
+  for (int j = 0; j < k; ++j) {
+    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
+    surv[j] = j;
+  }
+  for (int i = 0; i < m; ++i) want[i] = k + i;
+  std::shared_ptr<const Plan> plan;
+  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  GfwLocArgs a;
+  a.ws = static_cast<const uint8_t*>(workspace);
+  a.parity_stride = parity_stride;
+  a.per = per;
+  a.bs = (uint32_t)bs;  // bs < 2^32 (check_dev_batch), a multiple of 16 w
+  a.tiles = (uint32_t)((bs + kGfwLocTile - 1) / kGfwLocTile);
+  a.k = (uint32_t)k;
+  a.m = (uint32_t)m;
+  a.red = field(8).mul(0x80u, 2u);  // alpha^8 reduced: the polynomial's low byte
+  a.pad = 0;
+  for (size_t i = 0; i < (size_t)kGfwLocWords; ++i) a.ratio[i] = i < ratio->size() ? (*ratio)[i] : 0u;
+  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
+  // no grid above 2^31 - 1 workgroups: gfw_locate's (one 4 KiB tile of every
+  // block per workgroup), and verify_compare's bound, which keeps the encode
+  // plan's launches within theirs
+  const uint64_t cmp_tiles = (bs + kTileBytes - 1) / kTileBytes;
+  const uint64_t per_obj = a.tiles > (uint64_t)m * cmp_tiles ? a.tiles : (uint64_t)m * cmp_tiles;
+  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / per_obj;
+  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
+  if (chunk > max_obj) chunk = max_obj;
+  uint8_t* const ws = static_cast<uint8_t*>(workspace);
+  std::vector<Shard> enc(m);
+  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
+  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
+    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
+    std::vector<Shard> cin(in);
+    for (Shard& sh : cin) sh.base += o0 * obj_stride;
+    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
+    if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+    a.parity = parity + o0 * parity_stride;
+    if (launch_gfw_locate(w, a, no, lost + o0, s) != LEOEC_OK) return LEOEC_E_HIP;
+    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
+      return LEOEC_E_HIP;
+  }
+  return LEOEC_OK;
+}
+
+}  // namespace
+
 }  // namespace leoec
 
 extern "C" {
+
+int leoec_locate_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                   uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_locate_gfw_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                         uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                         uint32_t* lost, void* workspace, uint64_t workspace_bytes, void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_locate_gfw_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                    parity_stride, lost, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
+  });
+}
+
+int leoec_locate_wrows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
+  return leoec::guarded([&] { return leoec::op_locate_wrows(coding, k, m, w, ratio, cap); });
+}
 
 int leoec_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
                                   uint64_t* bytes) {

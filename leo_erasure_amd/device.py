@@ -232,6 +232,59 @@ def locate_ws(coding, params, objs, size, parity, nobj=None, lost=None, workspac
     return lost
 
 
+def locate_gfw_workspace(coding, params, size, nobj):
+    """leoec_locate_gfw_dev_workspace: bytes of workspace locate_gfw() wants
+    for one pass over the batch; locate_ws_workspace()'s value for everything
+    locate_ws() serves."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_locate_gfw_dev_workspace(_cid(coding), k, m, w, size, nobj,
+                                                  ctypes.byref(out)))
+    return out.value
+
+
+def locate_gfw(coding, params, objs, size, parity, nobj=None, lost=None, workspace=None,
+               stream=None):
+    """leoec_locate_gfw_dev: locate_ws()'s words, also for the GF(2^w) word
+    classes: vandrs w = 16 / 32 and vandrs / isars w = 8 with k > 16 or m > 4
+    (m >= 2, k + m <= 32), which need a workspace.  ``workspace`` (uint8)
+    follows verify()'s rules: allocated, up to ``VERIFY_WORKSPACE_CAP``, when
+    not given, and required on an explicit ``stream``.  Returns ``lost``,
+    which heal() takes as it is."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    if lost is None:
+        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    _words(lost, nobj, "lost")
+    need = locate_gfw_workspace(coding, params, size, nobj)
+    if need and workspace is None:
+        if stream is not None:
+            raise ValueError("locate_gfw on an explicit stream needs an explicit workspace "
+                             f"({need} B for one pass, at least {m * bs} B)")
+        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
+                                device=objs.device)
+    ws_ptr, ws_bytes = None, 0
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+            raise ValueError("workspace: contiguous uint8 device tensor expected")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
+    _lib.check(lib.leoec_locate_gfw_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
+                                        size, nobj, parity.data_ptr(), _row_stride(parity),
+                                        lost.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
+    return lost
+
+
+def locate_wrows(coding, params):
+    """leoec_locate_wrows (no device needed): the ratios locate_gfw() tests
+    the syndromes of the word classes with, ``m - 1`` lists of k GF(2^w)
+    coefficients, list i - 1 holding C[i][j] / C[0][j] of the coding matrix
+    C."""
+    k, m, w = params
+    cap = max((m - 1) * k, 1)
+    ratio = (ctypes.c_uint32 * cap)()
+    _lib.check(lib.leoec_locate_wrows(_cid(coding), k, m, w, ratio, cap))
+    return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
+
+
 def scrub_workspace(coding, params, size, nobj):
     """leoec_scrub_dev_workspace: bytes of workspace scrub() needs for ``nobj``
     objects (a 16-byte header and one index word per object)."""
