@@ -55,6 +55,20 @@ Shard block_shard(int id, int k, uint64_t bs, uint64_t size, const uint8_t* objs
   return Shard{parity + (uint64_t)(id - k) * bs, parity_stride, bs};
 }
 
+EncodeShards encode_shards(int k, int m, uint64_t bs, uint64_t size, const uint8_t* objs,
+                           uint64_t obj_stride, const uint8_t* parity, uint64_t parity_stride) {
+  EncodeShards e;
+  e.in.resize(k);
+  e.par.resize(m);
+  e.ids.resize(k + m);
+  for (int id = 0; id < k + m; ++id) {
+    (id < k ? e.in[id] : e.par[id - k]) =
+        block_shard(id, k, bs, size, objs, obj_stride, parity, parity_stride);
+    e.ids[id] = id;
+  }
+  return e;
+}
+
 int check_dev_batch(const uint8_t* objs, uint64_t obj_stride, uint64_t size, const uint8_t* parity,
                     uint64_t parity_stride, int m, uint64_t bs) {
   if (!objs || !parity) return LEOEC_E_ARG;
@@ -1424,17 +1438,8 @@ int op_encode_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   if ((rc = device_init())) return rc;
   const Code* c;
   if ((rc = get_code(coding, k, m, w, &c))) return rc;
-  std::vector<Shard> in(k), par(m);
-  std::vector<int> surv(k), want(m);
-  for (int j = 0; j < k; ++j) {
-    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
-    surv[j] = j;
-  }
-  for (int i = 0; i < m; ++i) {
-    par[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
-    want[i] = k + i;
-  }
-  return apply(*c, surv.data(), in, want.data(), par, bs, nobj, s);
+  const EncodeShards e = encode_shards(k, m, bs, size, objs, obj_stride, parity, parity_stride);
+  return apply(*c, e.surv(), e.in, e.want(), e.par, bs, nobj, s);
 }
 
 int op_decode_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,

@@ -124,6 +124,16 @@ uint64_t clamp_valid(uint64_t size, uint64_t start, uint64_t bs);
 // objs rows and is clipped to `size`, a coding id is whole, in the parity rows.
 Shard block_shard(int id, int k, uint64_t bs, uint64_t size, const uint8_t* objs,
                   uint64_t obj_stride, const uint8_t* parity, uint64_t parity_stride);
+// The encode direction of a device batch: the data blocks 0..k-1 in, the m
+// coding blocks out (block_shard), and their ids as make_plan / apply take them.
+struct EncodeShards {
+  std::vector<Shard> in, par;
+  std::vector<int> ids;  // 0..k+m-1
+  const int* surv() const { return ids.data(); }
+  const int* want() const { return ids.data() + in.size(); }
+};
+EncodeShards encode_shards(int k, int m, uint64_t bs, uint64_t size, const uint8_t* objs,
+                           uint64_t obj_stride, const uint8_t* parity, uint64_t parity_stride);
 // The batch checks of the verify / heal / locate entry points, in this order:
 // null or not 16-byte aligned bases, strides not multiples of 16
 // (LEOEC_E_ARG); bs >= 2^32 (LEOEC_E_BAD_SIZE); a stride shorter than its row

@@ -6,21 +6,20 @@
 //   fused    GF(2^8) matrix codes with k <= 16, m <= 4 (vandrs w = 8, isars):
 //            gf8_heal (heal_impl.hpp), one launch over the whole batch, the
 //            survivors, outputs and tables of every object taken from the
-//            code's pattern table (heal_table.hpp) on the device; never
-//            synchronises;
+//            code's pattern table (heal_table.hpp) on the device, cached
+//            per (code, device) (dev_table.hpp); never synchronises;
 //   generic  everything else: the masks come back to the host (one stream
 //            synchronisation), and every run of consecutive objects with the
 //            same mask goes through the ordinary plan of that erasure.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
-#include <map>
 #include <memory>
-#include <mutex>
 #include <tuple>
 #include <utility>
 #include <vector>
 
+#include "dev_table.hpp"
 #include "engine.hpp"
 #include "heal_impl.hpp"
 #include "knobs.hpp"
@@ -38,54 +37,21 @@ HealFn gf8_heal_pick(std::index_sequence<I...>, int k) {
   return sel[k - 1]();
 }
 
-// The pattern tables on the devices: one per (coding, k, m, device), built
-// and uploaded at the first heal that needs it and kept for the process.
-// Never evicted (a queued launch may still be reading one), so the cache is
-// bounded by count: past kMaxHealTables the caller takes the generic path.
-// The host image stays alive beside the device copy.
-constexpr size_t kMaxHealTables = 16;  // at most 16 x 8 MB of device memory
-
-struct HealTable {
-  std::vector<uint32_t> host;
-  uint32_t* dev = nullptr;
-};
-
 }  // namespace
 
-// LEOEC_OK and *out = the device image, or *out = nullptr when the cache is
-// full; a status when the build or the upload failed.
+// The pattern table of the code on the current device (dev_table.hpp), one per
+// (coding, k, m, device): nullptr when the cache is full, and the caller takes
+// the generic path.
 int heal_table(const Code& c, const uint32_t** out) {
-  static std::mutex mu;
-  static auto* cache = new std::map<std::tuple<int, int, int, int>, std::unique_ptr<HealTable>>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return LEOEC_E_HIP;
-  const auto key = std::make_tuple(c.coding, c.k, c.m, dev);
-  std::lock_guard<std::mutex> lock(mu);
-  const auto it = cache->find(key);
-  if (it != cache->end()) {
-    *out = it->second->dev;
-    return LEOEC_OK;
-  }
-  *out = nullptr;
-  if (cache->size() >= kMaxHealTables) return LEOEC_OK;
-  std::unique_ptr<HealTable> t(new HealTable);
-  const int rc = heal_build_table(
-      c.k, c.m,
-      [&c](const int* surv, const int* want, int nwant, std::vector<uint32_t>* rows) {
-        return gf_rows(c, surv, want, nwant, rows);
-      },
-      &t->host);
-  if (rc) return rc;
-  const size_t bytes = t->host.size() * sizeof(uint32_t);
-  if (hipMalloc(&t->dev, bytes) != hipSuccess) return LEOEC_E_NOMEM;
-  // a blocking copy: the image is on the device before any launch reads it
-  if (hipMemcpy(t->dev, t->host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    hip_drop(hipFree(t->dev));
-    return LEOEC_E_HIP;
-  }
-  *out = t->dev;
-  cache->emplace(key, std::move(t));
-  return LEOEC_OK;
+  // at most 16 x 8 MB of device memory; leaked: never destroyed at exit
+  static auto* const cache = new DevTableCache<std::tuple<int, int, int>, 16>;
+  const auto rows = [&c](const int* surv, const int* want, int nwant, std::vector<uint32_t>* r) {
+    return gf_rows(c, surv, want, nwant, r);
+  };
+  const auto build = [&](std::vector<uint32_t>* host) {
+    return heal_build_table(c.k, c.m, rows, host);
+  };
+  return cache->get(std::make_tuple(c.coding, c.k, c.m), build, out);
 }
 
 namespace {

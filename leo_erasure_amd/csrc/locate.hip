@@ -12,19 +12,21 @@
 //   locate_finish   all ones -> 0, exactly one bit -> kept, anything else ->
 //                   LEOEC_LOCATE_MANY.
 // leoec_locate_ws_dev adds the bitmatrix classes (cauchyrs, liberation), which
-// have no fused check: per chunk of objects that the caller's workspace holds,
-//   encode plan     the class's ordinary encode into the workspace (as
-//                   verify.hip's two-pass path);
+// have no fused check: the chunked encode pass (ws_pass.hpp, as verify.hip's
+// two-pass path), and per chunk of objects that the caller's workspace holds,
+//   encode plan     the pass's: the class's ordinary encode into the workspace;
 //   memset          the chunk's words to all ones;
 //   bit_locate      below: syndromes = workspace ^ stored coding blocks, the
 //                   packet form of the test (locate_bitrows.hpp);
 //   locate_finish.
 // Everything leoec_locate_dev serves is forwarded to it.
 // leoec_locate_gfw_dev adds the GF(2^w) word classes in the same way (vandrs
-// w = 16 / 32; vandrs / isars w = 8 with k > 16 or m > 4): the same four
-// steps with gfw_locate (locate_gfw_impl.hpp) in bit_locate's place, the word
-// form of the test (locate_wrows.hpp).  Everything leoec_locate_ws_dev serves
-// is forwarded to it.
+// w = 16 / 32; vandrs / isars w = 8 with k > 16 or m > 4): the same pass and
+// the same four steps with gfw_locate (locate_gfw_impl.hpp) in bit_locate's
+// place, the word form of the test (locate_wrows.hpp).  Everything
+// leoec_locate_ws_dev serves is forwarded to it.
+// The memset and the last step are one pair of helpers in all three calls
+// (locate_reset, locate_tail).
 // leoec_scrub_dev (scrub.hip) runs op_locate_dev with its own steps in it
 // (scrub_steps.hpp): its kernel stands in locate_finish's place;
 // leoec_scrub_ws_dev does the same with op_locate_ws_dev's bitmatrix branch.
@@ -43,6 +45,7 @@
 #include "locate_rows.hpp"
 #include "locate_wrows.hpp"
 #include "scrub_steps.hpp"
+#include "ws_pass.hpp"
 
 namespace leoec {
 
@@ -68,6 +71,27 @@ __global__ void __launch_bounds__(kThreads) locate_finish(uint32_t* __restrict__
   lost[i] = v == 0xFFFFFFFFu ? 0u : (v != 0u && (v & (v - 1u)) == 0u) ? v : LEOEC_LOCATE_MANY;
 }
 
+// The two ends of a chunk of `no` objects from object o0, in all three calls:
+// before its locate kernel, every word to all ones;
+int locate_reset(uint32_t* lost, uint64_t o0, uint64_t no, hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s);
+  return e == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
+}
+
+// after it, the caller's own step or locate_finish (no <= 2^31 - 1 words: one grid).
+int locate_tail(LocateSteps* steps, uint32_t* lost, uint64_t o0, uint64_t no, hipStream_t s) {
+  if (steps) return steps->finish(o0, no, s);
+  return launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, lost + o0, (uint32_t)no);
+}
+
+// The tail of leoec_locate_rows, _bitrows and _wrows: `need` words of room.
+int copy_rows(const std::vector<uint32_t>& t, uint32_t* out, int cap, int need) {
+  if (!out || cap < need) return LEOEC_E_ARG;
+  for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
+  return LEOEC_OK;
+}
+
 // The code and its ratio table; needs no device.
 int locate_code(int coding, int k, int m, int w, const Code** c, std::vector<uint32_t>* ratio) {
   int rc = check_params(coding, k, m, w);
@@ -83,9 +107,7 @@ int op_locate_rows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
   std::vector<uint32_t> t;
   const int rc = locate_code(coding, k, m, w, &c, &t);
   if (rc) return rc;
-  if (!ratio || cap < (m - 1) * k) return LEOEC_E_ARG;
-  for (size_t i = 0; i < t.size(); ++i) ratio[i] = t[i];
-  return LEOEC_OK;
+  return copy_rows(t, ratio, cap, (m - 1) * k);
 }
 
 }  // namespace
@@ -112,28 +134,18 @@ int op_locate_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   a.K = k;
   a.R = m;
   a.coef = c->C.a;  // the encoding rows: data blocks 0..k-1 in, coding blocks out
-  a.in.resize(k);
-  a.out.resize(m);
-  for (int j = 0; j < k; ++j)
-    a.in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
-  for (int i = 0; i < m; ++i)
-    a.out[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
+  EncodeShards sh = encode_shards(k, m, bs, size, objs, obj_stride, parity, parity_stride);
+  a.in = std::move(sh.in);
+  a.out = std::move(sh.par);
   a.block_size = bs;
   a.nobj = nobj;
   const LocateFn fn = gf8_locate_pick(std::make_index_sequence<kMaxK>{}, k, m);
   const uint64_t max_obj = gf8_max_objects(bs);
   for (uint64_t o0 = 0; o0 < nobj; o0 += max_obj) {
     const uint64_t no = nobj - o0 < max_obj ? nobj - o0 : max_obj;
-    if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+    if ((rc = locate_reset(lost, o0, no, s))) return rc;
     if ((rc = fn(a, ratio.data(), o0, no, lost, s))) return rc;
-    if (steps) {
-      if ((rc = steps->finish(o0, no, s))) return rc;
-      continue;
-    }
-    // no <= 2^31 - 1 words: one grid
-    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
-      return LEOEC_E_HIP;
+    if ((rc = locate_tail(steps, lost, o0, no, s))) return rc;
   }
   return LEOEC_OK;
 }
@@ -260,9 +272,7 @@ int op_locate_bitrows(int coding, int k, int m, int w, uint32_t* rows, int cap) 
   std::vector<uint32_t> t;
   const int rc = bit_locate_code(coding, k, m, w, &c, &t);
   if (rc) return rc;
-  if (!rows || cap < (m - 1) * k * w) return LEOEC_E_ARG;
-  for (size_t i = 0; i < t.size(); ++i) rows[i] = t[i];
-  return LEOEC_OK;
+  return copy_rows(t, rows, cap, (m - 1) * k * w);
 }
 
 int op_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
@@ -276,9 +286,8 @@ int op_locate_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, u
   if ((rc = bit ? bit_locate_code(coding, k, m, w, &c, &t) : locate_code(coding, k, m, w, &c, &t)))
     return rc;
   if (!bytes) return LEOEC_E_ARG;
-  uint64_t per, all;
-  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
-    return LEOEC_E_BAD_SIZE;
+  uint64_t all;
+  if (!encode_region_bytes(m, bs, nobj, &all)) return LEOEC_E_BAD_SIZE;
   *bytes = bit ? all : 0;
   return LEOEC_OK;
 }
@@ -305,60 +314,32 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
   if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
   if (steps && (rc = steps->check(bs))) return rc;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
-  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
-  if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per) return LEOEC_E_ARG;
+  if ((rc = WsPass::check(workspace, workspace_bytes, m, bs))) return rc;
   if ((rc = device_init())) return rc;
   if (steps && (rc = steps->begin(*c, s))) return rc;
-  std::vector<Shard> in(k);
-  std::vector<int> surv(k), want(m);
-  for (int j = 0; j < k; ++j) {
-    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
-    surv[j] = j;
-  }
-  for (int i = 0; i < m; ++i) want[i] = k + i;
-  std::shared_ptr<const Plan> plan;
-  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  WsPass pass;
+  if ((rc = pass.prepare(*c, bs, size, objs, obj_stride, parity, parity_stride))) return rc;
   BitLocArgs a;
   a.ws = static_cast<const uint8_t*>(workspace);
   a.parity_stride = parity_stride;
-  a.per = per;
+  a.per = (uint64_t)m * bs;
   a.ps = (uint32_t)(bs / (uint64_t)w);  // bs < 2^32 (check_dev_batch), a multiple of 16 w
   a.tiles = (a.ps + kBitLocTile - 1u) / kBitLocTile;
   a.k = (uint32_t)k;
   a.m = (uint32_t)m;
   a.w = (uint32_t)w;
   for (size_t i = 0; i < (size_t)kBitLocWords; ++i) a.rows[i] = i < rows.size() ? rows[i] : 0u;
-  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
-  // no grid above 2^31 - 1 workgroups: bit_locate's, and verify_compare's
-  // bound, which keeps the encode plan's launches within theirs
-  const uint64_t cmp_tiles = (bs + kTileBytes - 1) / kTileBytes;
-  const uint64_t per_obj = a.tiles > (uint64_t)m * cmp_tiles ? a.tiles : (uint64_t)m * cmp_tiles;
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / per_obj;
-  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
-  if (chunk > max_obj) chunk = max_obj;
-  uint8_t* const ws = static_cast<uint8_t*>(workspace);
-  std::vector<Shard> enc(m);
-  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
   const size_t lds = (size_t)w * kBitLocLanes * sizeof(u32x4);  // <= 32 KiB
-  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
-    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
-    std::vector<Shard> cin(in);
-    for (Shard& sh : cin) sh.base += o0 * obj_stride;
-    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
-    if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+  const auto chunk = [&](uint64_t o0, uint64_t no) {
+    int rc = locate_reset(lost, o0, no, s);
+    if (rc) return rc;
     a.parity = parity + o0 * parity_stride;
-    if (launch_kernel(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s, a,
-                      lost + o0) != LEOEC_OK)
-      return LEOEC_E_HIP;
-    if (steps) {
-      if ((rc = steps->finish(o0, no, s))) return rc;
-      continue;
-    }
-    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
-      return LEOEC_E_HIP;
-  }
-  return LEOEC_OK;
+    if ((rc = launch_kernel(bit_locate, dim3((uint32_t)(no * a.tiles)), dim3(kBitLocLanes), lds, s,
+                            a, lost + o0)))
+      return rc;
+    return locate_tail(steps, lost, o0, no, s);
+  };
+  return pass.run(workspace, workspace_bytes, nobj, a.tiles, s, chunk);
 }
 
 namespace {
@@ -418,9 +399,7 @@ int op_locate_wrows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
   const Code* c;
   const std::vector<uint32_t>* t;
   if ((rc = gfw_locate_code(coding, k, m, w, &c, &t))) return rc;
-  if (!ratio || cap < (m - 1) * k) return LEOEC_E_ARG;
-  for (size_t i = 0; i < t->size(); ++i) ratio[i] = (*t)[i];
-  return LEOEC_OK;
+  return copy_rows(*t, ratio, cap, (m - 1) * k);
 }
 
 int op_locate_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
@@ -434,11 +413,7 @@ int op_locate_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, 
   const std::vector<uint32_t>* t;
   if ((rc = gfw_locate_code(coding, k, m, w, &c, &t))) return rc;
   if (!bytes) return LEOEC_E_ARG;
-  uint64_t per, all;
-  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
-    return LEOEC_E_BAD_SIZE;
-  *bytes = all;
-  return LEOEC_OK;
+  return encode_region_bytes(m, bs, nobj, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
 }
 
 int launch_gfw_locate(int w, const GfwLocArgs& a, uint64_t no, uint32_t* lost, hipStream_t s) {
@@ -463,55 +438,30 @@ int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint
   if (nobj == 0 || bs == 0) return LEOEC_OK;
   if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
-  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
-  if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per) return LEOEC_E_ARG;
+  if ((rc = WsPass::check(workspace, workspace_bytes, m, bs))) return rc;
   if (ratio->size() > (size_t)kGfwLocWords) return LEOEC_E_UNSUPPORTED;  // (k + m <= 32: never)
   if ((rc = device_init())) return rc;
-  std::vector<Shard> in(k);
-  std::vector<int> surv(k), want(m);
-  for (int j = 0; j < k; ++j) {
-    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
-    surv[j] = j;
-  }
-  for (int i = 0; i < m; ++i) want[i] = k + i;
-  std::shared_ptr<const Plan> plan;
-  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  WsPass pass;
+  if ((rc = pass.prepare(*c, bs, size, objs, obj_stride, parity, parity_stride))) return rc;
   GfwLocArgs a;
   a.ws = static_cast<const uint8_t*>(workspace);
   a.parity_stride = parity_stride;
-  a.per = per;
+  a.per = (uint64_t)m * bs;
   a.bs = (uint32_t)bs;  // bs < 2^32 (check_dev_batch), a multiple of 16 w
-  a.tiles = (uint32_t)((bs + kGfwLocTile - 1) / kGfwLocTile);
+  a.tiles = (uint32_t)((bs + kGfwLocTile - 1) / kGfwLocTile);  // one 4 KiB tile of every block
   a.k = (uint32_t)k;
   a.m = (uint32_t)m;
   a.red = field(8).mul(0x80u, 2u);  // alpha^8 reduced: the polynomial's low byte
   a.pad = 0;
   for (size_t i = 0; i < (size_t)kGfwLocWords; ++i) a.ratio[i] = i < ratio->size() ? (*ratio)[i] : 0u;
-  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
-  // no grid above 2^31 - 1 workgroups: gfw_locate's (one 4 KiB tile of every
-  // block per workgroup), and verify_compare's bound, which keeps the encode
-  // plan's launches within theirs
-  const uint64_t cmp_tiles = (bs + kTileBytes - 1) / kTileBytes;
-  const uint64_t per_obj = a.tiles > (uint64_t)m * cmp_tiles ? a.tiles : (uint64_t)m * cmp_tiles;
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / per_obj;
-  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
-  if (chunk > max_obj) chunk = max_obj;
-  uint8_t* const ws = static_cast<uint8_t*>(workspace);
-  std::vector<Shard> enc(m);
-  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
-  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
-    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
-    std::vector<Shard> cin(in);
-    for (Shard& sh : cin) sh.base += o0 * obj_stride;
-    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
-    if (hipMemsetAsync(lost + o0, 0xFF, no * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
+  const auto chunk = [&](uint64_t o0, uint64_t no) {
+    int rc = locate_reset(lost, o0, no, s);
+    if (rc) return rc;
     a.parity = parity + o0 * parity_stride;
-    if (launch_gfw_locate(w, a, no, lost + o0, s) != LEOEC_OK) return LEOEC_E_HIP;
-    if (launch_kernel(locate_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                      dim3(kThreads), 0, s, lost + o0, (uint32_t)no) != LEOEC_OK)
-      return LEOEC_E_HIP;
-  }
-  return LEOEC_OK;
+    if ((rc = launch_gfw_locate(w, a, no, lost + o0, s))) return rc;
+    return locate_tail(nullptr, lost, o0, no, s);
+  };
+  return pass.run(workspace, workspace_bytes, nobj, a.tiles, s, chunk);
 }
 
 }  // namespace

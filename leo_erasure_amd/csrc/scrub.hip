@@ -26,25 +26,28 @@
 //                   object from the code's block table (scrub_bit_table.hpp),
 //                   from a fixed grid.
 // Workspace: the 16-byte header, one index word per object (rounded up to 16
-// bytes), then the encode region, m bs bytes per object of a chunk.  The block
-// tables are cached per (code, device) as heal's are, in a cache of their own;
-// when it is full the call is the composition: op_locate_ws_dev with
-// scrub_finish counting only, then op_heal_dev's generic path.
+// bytes), then the encode region, m bs bytes per object of a chunk (ws_pass.hpp).
+// The block tables are cached per (code, device) as heal's are (dev_table.hpp),
+// in a cache of their own; when it is full the call is the composition:
+// op_locate_ws_dev with scrub_finish counting only, then op_heal_dev's generic
+// path.
+// Both calls are one function, scrub_run: one ScrubSteps in the locate call,
+// which differs between them in the encode bytes of its workspace check, the
+// table it asks for and the heal-list kernel it launches.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
-#include <map>
-#include <memory>
-#include <mutex>
 #include <tuple>
 #include <utility>
 #include <vector>
 
+#include "dev_table.hpp"
 #include "engine.hpp"
 #include "knobs.hpp"
 #include "scrub_bit_impl.hpp"
 #include "scrub_impl.hpp"
 #include "scrub_steps.hpp"
+#include "ws_pass.hpp"
 
 namespace leoec {
 
@@ -128,98 +131,6 @@ int op_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint6
   return scrub_workspace(nobj, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
 }
 
-// leoec_scrub_dev's share of op_locate_dev.
-struct ScrubSteps final : LocateSteps {
-  int k = 0, m = 0;
-  uint8_t* objs = nullptr;
-  uint64_t obj_stride = 0, size = 0, bs = 0, nobj = 0;
-  uint8_t* parity = nullptr;
-  uint64_t parity_stride = 0;
-  uint32_t* report = nullptr;
-  uint32_t* totals = nullptr;
-  void* workspace = nullptr;
-  uint64_t workspace_bytes = 0;
-  bool begun = false;               // begin() ran: the device is open
-  const uint32_t* table = nullptr;  // heal's; nullptr after begin(): its cache is full
-  HealListFn heal = nullptr;
-
-  uint32_t* header() const { return static_cast<uint32_t*>(workspace); }
-  uint32_t* list() const { return header() + kScrubHeader / sizeof(uint32_t); }
-
-  int check(uint64_t block_size) override {
-    bs = block_size;
-    if (!totals || ((uintptr_t)totals & 3u)) return LEOEC_E_ARG;
-    if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
-    uint64_t need;
-    if (!scrub_workspace(nobj, &need)) return LEOEC_E_BAD_SIZE;
-    if (workspace_bytes < need) return LEOEC_E_ARG;
-    if (overlaps(report, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
-        overlaps(totals, 2 * sizeof(uint32_t), workspace, workspace_bytes))
-      return LEOEC_E_ARG;
-    return LEOEC_OK;
-  }
-
-  int begin(const Code& c, hipStream_t s) override {
-    const int rc = heal_table(c, &table);
-    if (rc) return rc;
-    begun = true;
-    heal = gf8_heal_list_pick(std::make_index_sequence<kMaxK>{}, k);
-    return hipMemsetAsync(totals, 0, 2 * sizeof(uint32_t), s) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
-  }
-
-  int finish(uint64_t o0, uint64_t no, hipStream_t s) override {
-    uint32_t* const words = report + o0;
-    if (table && hipMemsetAsync(header(), 0, kScrubHeader, s) != hipSuccess) return LEOEC_E_HIP;
-    // no <= 2^31 - 1 words: one grid
-    if (launch_kernel(scrub_finish, dim3((uint32_t)((no + kThreads - 1) / kThreads)),
-                      dim3(kThreads), 0, s, words, (uint32_t)no, table ? list() : nullptr, header(),
-                      totals) != LEOEC_OK)
-      return LEOEC_E_HIP;
-    if (!table) return LEOEC_OK;
-    HealArgs a;
-    a.objs = objs + o0 * obj_stride;
-    a.obj_stride = obj_stride;
-    a.parity = parity + o0 * parity_stride;
-    a.parity_stride = parity_stride;
-    a.lost = words;
-    a.unhealed = nullptr;
-    a.table = table;
-    a.size = size;
-    a.bs = (uint32_t)bs;
-    a.k = (uint32_t)k;
-    a.m = (uint32_t)m;
-    a.nobj = (uint32_t)no;
-    a.tiles = a.tmap = a.tperm = 0;  // the launcher's
-    const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
-    return heal(a, list(), header(), cap, s);
-  }
-};
-
-int op_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride, uint64_t size,
-                 uint64_t nobj, uint8_t* parity, uint64_t parity_stride, uint32_t* report,
-                 uint32_t* totals, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
-  ScrubSteps st;
-  st.k = k;
-  st.m = m;
-  st.objs = objs;
-  st.obj_stride = obj_stride;
-  st.size = size;
-  st.nobj = nobj;
-  st.parity = parity;
-  st.parity_stride = parity_stride;
-  st.report = report;
-  st.totals = totals;
-  st.workspace = workspace;
-  st.workspace_bytes = workspace_bytes;
-  const int rc = op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
-                         report, s, &st);
-  if (rc || !st.begun || st.table) return rc;
-  // heal's table cache is full: the words are final and counted; the rest is
-  // leoec_heal_dev's generic path (one synchronisation)
-  return op_heal_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
-                     st.list(), s);
-}
-
 // ---------------------------------------------------------------------------
 // The bitmatrix classes: leoec_scrub_ws_dev.
 
@@ -238,53 +149,19 @@ int scrub_bit_fn(const Code& c, const int* surv, int block, std::vector<uint8_t>
   return bit_rows(c, surv, &block, 1, rows);
 }
 
-// The block tables on the devices: one per (coding, k, m, w, device), built
-// and uploaded at the first scrub that needs it and kept for the process, as
-// heal.hip keeps its pattern tables and beside them: never evicted (a queued
-// launch may still be reading one), bounded by count (at most 16 x 95 KB of
-// device memory), past which the caller runs the composition.
-constexpr size_t kMaxScrubBitTables = 16;
-
-struct ScrubBitTable {
-  std::vector<uint32_t> host;
-  uint32_t* dev = nullptr;
-};
-
-// LEOEC_OK and *out = the device image, or *out = nullptr when the cache is
-// full; a status when the build or the upload failed.
+// The block table of the code on the current device (dev_table.hpp), one per
+// (coding, k, m, w, device), in a cache of their own beside heal's pattern
+// tables: nullptr when it is full, and the caller runs the composition.
 int scrub_bit_table(const Code& c, const uint32_t** out) {
-  static std::mutex mu;
-  static auto* cache =
-      new std::map<std::tuple<int, int, int, int, int>, std::unique_ptr<ScrubBitTable>>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return LEOEC_E_HIP;
-  const auto key = std::make_tuple(c.coding, c.k, c.m, c.w, dev);
-  std::lock_guard<std::mutex> lock(mu);
-  const auto it = cache->find(key);
-  if (it != cache->end()) {
-    *out = it->second->dev;
-    return LEOEC_OK;
-  }
-  *out = nullptr;
-  if (cache->size() >= kMaxScrubBitTables) return LEOEC_OK;
-  std::unique_ptr<ScrubBitTable> t(new ScrubBitTable);
-  const int rc = scrub_bit_build_table(
-      c.k, c.m, c.w,
-      [&c](const int* surv, int block, std::vector<uint8_t>* rows) {
-        return scrub_bit_fn(c, surv, block, rows);
-      },
-      &t->host);
-  if (rc) return rc;
-  const size_t bytes = t->host.size() * sizeof(uint32_t);
-  if (hipMalloc(&t->dev, bytes) != hipSuccess) return LEOEC_E_NOMEM;
-  // a blocking copy: the image is on the device before any launch reads it
-  if (hipMemcpy(t->dev, t->host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-    hip_drop(hipFree(t->dev));
-    return LEOEC_E_HIP;
-  }
-  *out = t->dev;
-  cache->emplace(key, std::move(t));
-  return LEOEC_OK;
+  // at most 16 x 95 KB of device memory; leaked: never destroyed at exit
+  static auto* const cache = new DevTableCache<std::tuple<int, int, int, int>, 16>;
+  const auto rows = [&c](const int* surv, int block, std::vector<uint8_t>* r) {
+    return scrub_bit_fn(c, surv, block, r);
+  };
+  const auto build = [&](std::vector<uint32_t>* host) {
+    return scrub_bit_build_table(c.k, c.m, c.w, rows, host);
+  };
+  return cache->get(std::make_tuple(c.coding, c.k, c.m, c.w), build, out);
 }
 
 // Header and index words for nobj objects plus an encode region of `enc`
@@ -300,15 +177,20 @@ int op_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, ui
   int rc = bit_scrub_served(coding, k, m, w, size);
   if (rc) return rc;
   if (!bytes) return LEOEC_E_ARG;
-  uint64_t bs = 0, per, enc;
+  uint64_t bs = 0, enc;
   if ((rc = op_layout(coding, k, m, w, size, &bs, nullptr))) return rc;
-  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &enc))
-    return LEOEC_E_BAD_SIZE;
+  if (!encode_region_bytes(m, bs, nobj, &enc)) return LEOEC_E_BAD_SIZE;
   return scrub_ws_workspace(nobj, enc, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
 }
 
-// leoec_scrub_ws_dev's share of op_locate_ws_dev's bitmatrix branch.
-struct BitScrubSteps final : LocateSteps {
+// ---------------------------------------------------------------------------
+// Both calls.
+
+// The scrub calls' share of the locate call they run (scrub_steps.hpp):
+// leoec_scrub_dev's of op_locate_dev, and with `bit` leoec_scrub_ws_dev's of
+// op_locate_ws_dev's bitmatrix branch.
+struct ScrubSteps final : LocateSteps {
+  bool bit = false;
   int k = 0, m = 0, w = 0;
   uint8_t* objs = nullptr;
   uint64_t obj_stride = 0, size = 0, bs = 0, nobj = 0;
@@ -319,7 +201,8 @@ struct BitScrubSteps final : LocateSteps {
   void* workspace = nullptr;
   uint64_t workspace_bytes = 0;
   bool begun = false;               // begin() ran: the device is open
-  const uint32_t* table = nullptr;  // nullptr after begin(): the cache is full
+  const uint32_t* table = nullptr;  // heal's, bit: the block table; nullptr after begin(): cache full
+  HealListFn heal = nullptr;        // !bit
 
   uint32_t* header() const { return static_cast<uint32_t*>(workspace); }
   uint32_t* list() const { return header() + kScrubHeader / sizeof(uint32_t); }
@@ -328,8 +211,8 @@ struct BitScrubSteps final : LocateSteps {
     bs = block_size;
     if (!totals || ((uintptr_t)totals & 3u)) return LEOEC_E_ARG;
     if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
-    uint64_t per, need;  // the header, the index words and one object's encode
-    if (__builtin_mul_overflow((uint64_t)m, bs, &per) || !scrub_ws_workspace(nobj, per, &need))
+    uint64_t enc = 0, need;  // the header and the index words; bit: and one object's encode
+    if ((bit && !encode_region_bytes(m, bs, 1, &enc)) || !scrub_ws_workspace(nobj, enc, &need))
       return LEOEC_E_BAD_SIZE;
     if (workspace_bytes < need) return LEOEC_E_ARG;
     if (overlaps(report, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
@@ -339,9 +222,10 @@ struct BitScrubSteps final : LocateSteps {
   }
 
   int begin(const Code& c, hipStream_t s) override {
-    const int rc = scrub_bit_table(c, &table);
+    const int rc = bit ? scrub_bit_table(c, &table) : heal_table(c, &table);
     if (rc) return rc;
     begun = true;
+    if (!bit) heal = gf8_heal_list_pick(std::make_index_sequence<kMaxK>{}, k);
     return hipMemsetAsync(totals, 0, 2 * sizeof(uint32_t), s) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
   }
 
@@ -354,40 +238,41 @@ struct BitScrubSteps final : LocateSteps {
                       totals) != LEOEC_OK)
       return LEOEC_E_HIP;
     if (!table) return LEOEC_OK;
+    HealArgs h;
+    h.objs = objs + o0 * obj_stride;
+    h.obj_stride = obj_stride;
+    h.parity = parity + o0 * parity_stride;
+    h.parity_stride = parity_stride;
+    h.lost = words;
+    h.unhealed = nullptr;
+    h.table = table;
+    h.size = size;
+    h.bs = (uint32_t)bs;  // < 2^32 (check_dev_batch); bit: a multiple of 16 w
+    h.k = (uint32_t)k;
+    h.m = (uint32_t)m;
+    h.nobj = (uint32_t)no;
+    h.tiles = h.tmap = h.tperm = 0;  // the launcher's
+    const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
+    if (!bit) return heal(h, list(), header(), cap, s);
     BitHealArgs a;
-    a.h.objs = objs + o0 * obj_stride;
-    a.h.obj_stride = obj_stride;
-    a.h.parity = parity + o0 * parity_stride;
-    a.h.parity_stride = parity_stride;
-    a.h.lost = words;
-    a.h.unhealed = nullptr;
-    a.h.table = table;
-    a.h.size = size;
-    a.h.bs = (uint32_t)bs;  // < 2^32 (check_dev_batch), a multiple of 16 w
-    a.h.k = (uint32_t)k;
-    a.h.m = (uint32_t)m;
+    a.h = h;
     a.w = (uint32_t)w;
     a.ps = (uint32_t)(bs / (uint64_t)w);
     a.h.tiles = (a.ps + kBitHealTile - 1u) / kBitHealTile;  // bit_locate's: no x tiles < 2^31
-    a.h.nobj = (uint32_t)no;
-    a.h.tmap = a.h.tperm = 0;
     a.rec_words = scrub_bit_record_words(k, w);
     a.pad = 0;
-    const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
     return launch_bit_heal_list(a, list(), header(), cap, s);
   }
 };
 
-int op_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
-                    uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
-                    uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
-                    hipStream_t s) {
-  if (!bit_class(coding))  // served or LEOEC_E_UNSUPPORTED there
-    return op_scrub_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
-                        totals, workspace, workspace_bytes, s);
-  int rc = bit_scrub_served(coding, k, m, w, size);
-  if (rc) return rc;
-  BitScrubSteps st;
+// Both calls after their own served tests: the locate call with the steps in
+// it, then, when the table cache was full, leoec_heal_dev's generic path.
+int scrub_run(bool bit, int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+              uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+              uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
+              hipStream_t s) {
+  ScrubSteps st;
+  st.bit = bit;
   st.k = k;
   st.m = m;
   st.w = w;
@@ -401,22 +286,44 @@ int op_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj
   st.totals = totals;
   st.workspace = workspace;
   st.workspace_bytes = workspace_bytes;
-  // the encode region behind the header and the index words (check() refuses
-  // a workspace that has none before anything looks at it)
+  // bit: the encode region behind the header and the index words (check()
+  // refuses a workspace that has none before anything looks at it)
   uint64_t head;
   void* enc = nullptr;
   uint64_t enc_bytes = 0;
-  if (workspace && scrub_workspace(nobj, &head) && workspace_bytes > head) {
+  if (bit && workspace && scrub_workspace(nobj, &head) && workspace_bytes > head) {
     enc = static_cast<uint8_t*>(workspace) + head;
     enc_bytes = workspace_bytes - head;
   }
-  rc = op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
-                        enc, enc_bytes, s, &st);
+  const int rc = bit ? op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                        parity_stride, report, enc, enc_bytes, s, &st)
+                     : op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                     parity_stride, report, s, &st);
   if (rc || !st.begun || st.table) return rc;
   // the table cache is full: the words are final and counted; the rest is
   // leoec_heal_dev's generic path (one synchronisation)
   return op_heal_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
                      st.list(), s);
+}
+
+int op_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride, uint64_t size,
+                 uint64_t nobj, uint8_t* parity, uint64_t parity_stride, uint32_t* report,
+                 uint32_t* totals, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+  return scrub_run(false, coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+                   report, totals, workspace, workspace_bytes, s);
+}
+
+int op_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                    uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                    uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
+                    hipStream_t s) {
+  if (!bit_class(coding))  // served or LEOEC_E_UNSUPPORTED there
+    return op_scrub_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                        totals, workspace, workspace_bytes, s);
+  const int rc = bit_scrub_served(coding, k, m, w, size);
+  if (rc) return rc;
+  return scrub_run(true, coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
+                   totals, workspace, workspace_bytes, s);
 }
 
 int op_scrub_bitrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* rows,

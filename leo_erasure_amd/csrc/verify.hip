@@ -6,9 +6,9 @@
 //   fused     GF(2^8) matrix codes with k <= 16, m <= 4 (vandrs w = 8, isars):
 //             gf8_check (verify_impl.hpp) reads the k + m blocks once and
 //             writes nothing for a clean stripe; no workspace;
-//   two-pass  everything else: the ordinary encode plan into the caller's
-//             workspace, then verify_compare against the stored blocks, a
-//             chunk of objects at a time in stream order.
+//   two-pass  everything else: the chunked encode pass (ws_pass.hpp) into the
+//             caller's workspace, with verify_compare against the stored
+//             blocks as each chunk's launch.
 // This unit is kept out of engine.cpp / capi.cpp: the host sanitizer harness
 // (tests/host_sanitize) links those against stand-in kernels and a stand-in
 // HIP header that know nothing of these launches.  For the same reason the
@@ -18,6 +18,7 @@
 #include "engine.hpp"
 #include "knobs.hpp"
 #include "verify_impl.hpp"
+#include "ws_pass.hpp"
 
 namespace leoec {
 
@@ -71,9 +72,8 @@ int op_verify_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint
   const int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
   if (rc) return rc;
   if (!bytes) return LEOEC_E_ARG;
-  uint64_t per, all;
-  if (__builtin_mul_overflow((uint64_t)m, bs, &per) || __builtin_mul_overflow(per, nobj, &all))
-    return LEOEC_E_BAD_SIZE;
+  uint64_t all;
+  if (!encode_region_bytes(m, bs, nobj, &all)) return LEOEC_E_BAD_SIZE;
   *bytes = verify_fused(coding, k, m, w) ? 0 : all;
   return LEOEC_OK;
 }
@@ -87,35 +87,23 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
   if (nobj == 0 || bs == 0) return LEOEC_OK;
   if (!flags || ((uintptr_t)flags & 3u)) return LEOEC_E_ARG;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
-  const uint64_t per = (uint64_t)m * bs;  // workspace bytes of one object
   const bool fused = verify_fused(coding, k, m, w);
-  if (!fused && (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < per))
-    return LEOEC_E_ARG;
+  if (!fused && (rc = WsPass::check(workspace, workspace_bytes, m, bs))) return rc;
   if ((rc = device_init())) return rc;
   const Code* c;
   if ((rc = get_code(coding, k, m, w, &c))) return rc;
-  std::vector<Shard> in(k), par(m);
-  std::vector<int> surv(k), want(m);
-  for (int j = 0; j < k; ++j) {
-    in[j] = block_shard(j, k, bs, size, objs, obj_stride, parity, parity_stride);
-    surv[j] = j;
-  }
-  for (int i = 0; i < m; ++i) {
-    par[i] = block_shard(k + i, k, bs, size, objs, obj_stride, parity, parity_stride);
-    want[i] = k + i;
-  }
-  std::shared_ptr<const Plan> plan;
-  if ((rc = make_plan(*c, surv.data(), want.data(), m, &plan))) return rc;
+  WsPass pass;
+  if ((rc = pass.prepare(*c, bs, size, objs, obj_stride, parity, parity_stride))) return rc;
   if (hipMemsetAsync(flags, 0, nobj * sizeof(uint32_t), s) != hipSuccess) return LEOEC_E_HIP;
   if (fused) {
-    if (plan->kind != Plan::kGf) return LEOEC_E_UNSUPPORTED;
+    if (pass.plan->kind != Plan::kGf) return LEOEC_E_UNSUPPORTED;
     GfApply a;
     a.w = w;
     a.K = k;
     a.R = m;
-    a.coef = plan->coef;
-    a.in = in;
-    a.out = par;
+    a.coef = pass.plan->coef;
+    a.in = std::move(pass.sh.in);
+    a.out = std::move(pass.sh.par);
     a.block_size = bs;
     a.nobj = nobj;
     const CheckFn fn = gf8_check_pick(std::make_index_sequence<kMaxK>{}, k, m);
@@ -127,24 +115,13 @@ int op_verify_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t
     return LEOEC_OK;
   }
   const uint32_t tiles = (uint32_t)((bs + kTileBytes - 1) / kTileBytes);
-  uint64_t chunk = workspace_bytes / per;  // objects per pass (>= 1)
-  const uint64_t max_obj = (uint64_t)0x7FFFFFFF / ((uint64_t)m * tiles);
-  if (max_obj == 0) return LEOEC_E_BAD_SIZE;
-  if (chunk > max_obj) chunk = max_obj;
-  uint8_t* const ws = static_cast<uint8_t*>(workspace);
-  std::vector<Shard> enc(m);
-  for (int i = 0; i < m; ++i) enc[i] = Shard{ws + (uint64_t)i * bs, per, bs};
-  for (uint64_t o0 = 0; o0 < nobj; o0 += chunk) {
-    const uint64_t no = nobj - o0 < chunk ? nobj - o0 : chunk;
-    std::vector<Shard> cin(in);
-    for (Shard& sh : cin) sh.base += o0 * obj_stride;
-    if ((rc = run_plan(*plan, cin, enc, bs, no, s))) return rc;
-    if (launch_kernel(verify_compare, dim3((uint32_t)(no * m * tiles)), dim3(kThreads), 0, s, ws,
-                      parity + o0 * parity_stride, parity_stride, (uint32_t)bs, (uint32_t)m, tiles,
-                      flags + o0) != LEOEC_OK)
-      return LEOEC_E_HIP;
-  }
-  return LEOEC_OK;
+  const uint8_t* const ws = static_cast<const uint8_t*>(workspace);
+  const auto compare = [&](uint64_t o0, uint64_t no) {
+    return launch_kernel(verify_compare, dim3((uint32_t)(no * m * tiles)), dim3(kThreads), 0, s, ws,
+                         parity + o0 * parity_stride, parity_stride, (uint32_t)bs, (uint32_t)m,
+                         tiles, flags + o0);
+  };
+  return pass.run(workspace, workspace_bytes, nobj, (uint64_t)m * tiles, s, compare);
 }
 
 }  // namespace

@@ -75,23 +75,25 @@ def test_device_locate_ws_partial_batch(gpu, le, oracle, family):
 @pytest.mark.gpu
 def test_device_locate_ws_chunked_workspace(gpu, le, oracle, family):
     """A workspace of exactly m bs bytes, one object per chunk and five chunks,
-    gives the words of the one-pass workspace (the query's size)."""
+    and one of 3 m bs bytes, a chunk of three objects and a ragged one of two,
+    give the words of the one-pass workspace (the query's size)."""
     errors = []
     for case in _cases(le, oracle, family):
         n, m, bs = case.n, case.m, case.bs
+        assert n == 5
         assert le.device.locate_ws_workspace(case.cls, case.params, case.size, n) == n * m * bs
         dmg, want = L.expected_calls(case)[2]
         work, par = L.damaged_arenas(gpu, case, dmg)
         got = []
-        for nbytes in (n * m * bs, m * bs):
+        for nbytes in (n * m * bs, m * bs, 3 * m * bs):
             ws = gpu.full((nbytes,), 0xEE, dtype=gpu.uint8, device="cuda")
             _, words, err = W.run_locate_ws(gpu, le, case, work, par, workspace=ws)
             if err:
                 errors.append(err)
             got.append(words)
-        if got[0] != want or got[1] != want:
+        if got[0] != want or got[1] != want or got[2] != want:
             errors.append(f"{case.ident()}: one pass {_hex(got[0])}, five chunks {_hex(got[1])}, "
-                          f"expected {_hex(want)}")
+                          f"chunks of three and two {_hex(got[2])}, expected {_hex(want)}")
     assert not errors, "\n".join(errors[:20])
 
 
