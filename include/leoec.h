@@ -132,7 +132,16 @@ int leoec_repair(int coding, int k, int m, int w, const uint8_t *const *blocks, 
  * Strides cover a whole row (obj_stride >= size, parity_stride >=
  * m*block_size, block/out strides >= block_size) for every nobj >= 1;
  * otherwise LEOEC_E_ARG.  The buffers themselves cannot be checked here:
- * they must hold nobj rows.                                                */
+ * they must hold nobj rows.
+ * leoec_encode_dev, leoec_decode_dev, leoec_repair_dev, leoec_verify_dev
+ * (with and without a workspace) and leoec_heal_dev where it takes one launch
+ * (see there) allocate nothing, upload nothing and wait for nothing: every
+ * memset and every launch, the several launches of a large code (k > 16,
+ * m > 4) or of a chunked workspace included, goes to `stream` in order, the
+ * coefficients travel as kernel arguments.  So these calls can be captured
+ * into a graph, after the first call: the first call of a code on a device
+ * builds its plan on the host (and heal its device table, with a blocking
+ * copy) and loads the code objects it needs.                               */
 
 /* Encode nobj objects of `size` bytes each, stored at objs + o*obj_stride
  * (the unpadded object; bytes past `size` inside the last data block are

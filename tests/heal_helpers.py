@@ -54,6 +54,35 @@ def edge_masks(k, m):
             bits([0, k + m])]
 
 
+RUN_N = 12  # objects per batch of run_masks
+
+
+def run_masks(k, m):
+    """The per-object masks of a RUN_N-object batch with runs of equal masks
+    (pure), what a scrub after a lost disk hands to heal: a = {k-1} three
+    times, two clean objects, b = {0, k-1} plus coding blocks up to m twice,
+    U = m + 1 blocks (unrecoverable) twice, c = all m coding blocks once, a
+    twice.  A run at the front and one at the back, a clean and an
+    unrecoverable run, every run abutting the next; with nobj = RUN_N - 1 the
+    last run is cut."""
+    a = bits([k - 1])
+    b = bits(([0, k - 1] + list(range(k, k + m)))[:m])
+    c = bits(range(k, k + m))
+    U = bits(range(k - 1, k + m))
+    return [a, a, a, 0, 0, b, b, U, U, c, a, a]
+
+
+def runs_of(masks):
+    """[(mask, first object, objects)] of the runs of consecutive equal masks."""
+    out = []
+    for o, mask in enumerate(masks):
+        if out and out[-1][0] == mask:
+            out[-1][2] += 1
+        else:
+            out.append([mask, o, 1])
+    return [tuple(r) for r in out]
+
+
 def recoverable(mask, k, m):
     return bin(mask).count("1") <= m and mask >> (k + m) == 0
 

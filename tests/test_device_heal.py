@@ -12,10 +12,17 @@ launch.  Which path serves which row (heal.hip):
   everything else                                   masks copied back, one
                                                     plan launch per run
 
-Every batch has heal_helpers.EDGE_N = 9 objects, one per mask of
+The edge batches have heal_helpers.EDGE_N = 9 objects, one per mask of
 heal_helpers.edge_masks: clean, six recoverable patterns (data and coding
-blocks, ragged and empty outputs) and two unrecoverable ones.  All
-expectations are the oracle's blocks (the snapshots of the EdgeCase)."""
+blocks, ragged and empty outputs) and two unrecoverable ones.  No two of those
+masks are equal, so on the generic path every damaged object is a run of its
+own: one launch each, no > 1 never reached.  The run batches have
+heal_helpers.RUN_N = 12 objects with heal_helpers.run_masks: runs of two and
+three equal masks (one launch over several objects at a base offset of
+first * stride), a clean run, an unrecoverable run, a run whose only lost block
+lies past `size` at the small sizes (nothing to launch, unhealed still 0), and
+a run cut by nobj.  All expectations are the oracle's blocks (the snapshots of
+the EdgeCase)."""
 import pytest
 
 import gpu_helpers as H
@@ -29,10 +36,10 @@ def family(request):
     return request.param
 
 
-def _cases(le, oracle, family):
+def _cases(le, oracle, family, n=P.EDGE_N):
     cls, k, m, w, B = family
     for size in H.edge_sizes(k, w, B):
-        yield H.edge_case(le, oracle, family[:4], size, n=P.EDGE_N)
+        yield H.edge_case(le, oracle, family[:4], size, n=n)
 
 
 def test_edge_masks_are_what_they_claim():
@@ -54,6 +61,32 @@ def test_edge_masks_are_what_they_claim():
         assert len(set(masks)) == P.EDGE_N  # no run of equal masks: one launch each on the generic path
     assert sum(P.fused(*f[:4]) for f in P.FAMILIES) == 5  # the 64-lane row included
     assert all(P.fused(*f[:4]) for f in P.GF8_FAMILIES)
+
+
+def test_run_masks_are_what_they_claim(le):
+    """No GPU: the run list of every family, spelled out: a run at the front
+    and one at the back, a clean run, an unrecoverable run, every run abutting
+    the next; and at the two smallest sizes block k-1 holds no byte below
+    `size`, so the runs of {k-1} have nothing to write."""
+    for cls, k, m, w, B in P.FAMILIES:
+        masks = P.run_masks(k, m)
+        assert len(masks) == P.RUN_N == 12
+        a, b, c, U = masks[0], masks[5], masks[9], masks[7]
+        assert masks == [a, a, a, 0, 0, b, b, U, U, c, a, a]
+        assert P.ids_of(a) == [k - 1]
+        assert P.ids_of(b) == sorted(([0, k - 1] + list(range(k, k + m)))[:m]) and len(P.ids_of(b)) == m
+        assert P.ids_of(c) == list(range(k, k + m))
+        assert P.ids_of(U) == list(range(k - 1, k + m))
+        assert [P.recoverable(x, k, m) for x in (a, 0, b, U, c)] == [True, True, True, False, True]
+        assert P.runs_of(masks) == [(a, 0, 3), (0, 3, 2), (b, 5, 2), (U, 7, 2), (c, 9, 1), (a, 10, 2)]
+        assert len({a, 0, b, U, c}) == 5
+        # nobj = RUN_N - 1 cuts the last run: object 10 alone is healed
+        assert P.runs_of(masks[:P.RUN_N - 1])[-1] == (a, 10, 1)
+        sizes = H.edge_sizes(k, w, B)
+        for size in sorted(sizes)[:2]:
+            bs, _ = le.layout(cls, (k, m, w), size)
+            assert H.block_valids(k, bs, size)[k - 1] == 0 and (k - 1) * bs >= size
+        assert H.block_valids(k, B, sizes[0])[k - 1] == B  # and at the large sizes it has bytes
 
 
 @pytest.mark.gpu
@@ -79,6 +112,31 @@ def test_device_heal_partial_batch(gpu, le, oracle, family):
     errors = []
     for case in _cases(le, oracle, family):
         errors += P.run_heal(gpu, le, case, masks, nobj=case.n - 2)
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_heal_runs(gpu, le, oracle, family):
+    """run_masks over 12 objects at every size: the generic path's runs of
+    two and three objects go out as one launch each, at first * stride; the
+    clean and the unrecoverable run launch nothing; at the small sizes {k-1}
+    is an empty block, its runs launch nothing and unhealed is 0 all the
+    same.  (The fused rows take gf8_heal: the same batch, one launch.)"""
+    cls, k, m, w, B = family
+    errors = []
+    for case in _cases(le, oracle, family, n=P.RUN_N):
+        errors += P.run_heal(gpu, le, case, P.run_masks(k, m))
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+def test_device_heal_runs_cut_by_nobj(gpu, le, oracle, family):
+    """nobj = 11: the last run is cut in two; object 10 is healed, object 11
+    keeps its poison and its word its pre-fill."""
+    cls, k, m, w, B = family
+    errors = []
+    for case in _cases(le, oracle, family, n=P.RUN_N):
+        errors += P.run_heal(gpu, le, case, P.run_masks(k, m), nobj=P.RUN_N - 1)
     assert not errors, "\n".join(errors[:20])
 
 
