@@ -134,14 +134,18 @@ int leoec_repair(int coding, int k, int m, int w, const uint8_t *const *blocks, 
  * otherwise LEOEC_E_ARG.  The buffers themselves cannot be checked here:
  * they must hold nobj rows.
  * leoec_encode_dev, leoec_decode_dev, leoec_repair_dev, leoec_verify_dev
- * (with and without a workspace) and leoec_heal_dev where it takes one launch
- * (see there) allocate nothing, upload nothing and wait for nothing: every
+ * (with and without a workspace), the three locate and the three scrub calls
+ * (leoec_scrub_gfw_dev serves every class a locate call names one block for,
+ * up to k + m = 31) and leoec_heal_dev where it takes one launch (see there:
+ * vandrs w = 8 and isars with k <= 16, m <= 4; the other classes are healed
+ * without a synchronisation through the scrub calls only)
+ * allocate nothing, upload nothing and wait for nothing: every
  * memset and every launch, the several launches of a large code (k > 16,
  * m > 4) or of a chunked workspace included, goes to `stream` in order, the
  * coefficients travel as kernel arguments.  So these calls can be captured
  * into a graph, after the first call: the first call of a code on a device
- * builds its plan on the host (and heal its device table, with a blocking
- * copy) and loads the code objects it needs.                               */
+ * builds its plan on the host (and heal and the scrub calls their device
+ * tables, with a blocking copy) and loads the code objects it needs.       */
 
 /* Encode nobj objects of `size` bytes each, stored at objs + o*obj_stride
  * (the unpadded object; bytes past `size` inside the last data block are
@@ -394,8 +398,8 @@ int leoec_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, ui
  * misaligned, report or totals inside the workspace, or workspace_bytes below
  * the query's: LEOEC_E_ARG.
  * Served: what leoec_locate_dev serves, vandrs w = 8 and isars with k <= 16
- * and 2 <= m <= 4.  Everything else (cauchyrs and liberation included: they
- * would need leoec_locate_ws_dev and a synchronising heal) is
+ * and 2 <= m <= 4.  Everything else (cauchyrs and liberation: leoec_scrub_ws_dev;
+ * vandrs w = 16 / 32, k > 16, m > 4: leoec_scrub_gfw_dev; m = 1) is
  * LEOEC_E_UNSUPPORTED, returned before the device is opened; invalid
  * parameters keep their leoec_check_params status; nobj == 0 is LEOEC_OK with
  * nothing written.  The checks come in leoec_locate_dev's order: layout and
@@ -453,9 +457,9 @@ int leoec_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size,
  *       where the bit of id 31 is LEOEC_LOCATE_MANY's own word, so an object
  *       that names block 31 and one that names none could not be told apart
  *       and the totals could not be counted.
- * Everything else (vandrs w = 16 / 32, w = 8 with k > 16 or m > 4 or m = 1,
- * bitmatrix m = 1, k + m >= 32, a table above 768 words such as
- * cauchyrs(10,4,32)) is LEOEC_E_UNSUPPORTED, returned before the device is
+ * Everything else (vandrs w = 16 / 32 and w = 8 with k > 16 or m > 4, which
+ * leoec_scrub_gfw_dev serves; m = 1, bitmatrix k + m >= 32, a table above 768
+ * words such as cauchyrs(10,4,32)) is LEOEC_E_UNSUPPORTED, returned before the device is
  * opened; invalid parameters keep their leoec_check_params status; nobj == 0
  * is LEOEC_OK with nothing written.  The checks come in leoec_scrub_dev's
  * order: layout and parameters, served, empty batch, pointers and strides,
@@ -491,7 +495,92 @@ int leoec_scrub_ws_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t 
                        uint32_t *report, uint32_t *totals, void *workspace,
                        uint64_t workspace_bytes, void *stream);
 
+/* Workspace bytes leoec_scrub_gfw_dev wants for this batch: for everything
+ * leoec_scrub_ws_dev serves, that call's query (same value, same statuses);
+ * for class (c) below 16 + round_up(4 * nobj, 16) + nobj * m * block_size
+ * (one pass); LEOEC_E_BAD_SIZE when that overflows; bytes == NULL:
+ * LEOEC_E_ARG, checked after the served checks.  Configurations
+ * leoec_scrub_gfw_dev does not serve, and invalid ones, get its statuses.
+ * Needs no device. */
+int leoec_scrub_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                  uint64_t *bytes);
+
+/* leoec_scrub_ws_dev plus the GF(2^w) word classes, in the relation
+ * leoec_locate_gfw_dev has to leoec_locate_ws_dev.  The contract is the
+ * composition leoec_locate_gfw_dev then leoec_heal_dev(lost = report), byte
+ * for byte: after the call
+ *   report[o]  is leoec_locate_gfw_dev's word for object o of the batch as it
+ *              was before the call: 0, one bit b < k + m, or LEOEC_LOCATE_MANY;
+ *   objs and parity hold the bytes leoec_heal_dev(..., lost = report, ...)
+ *              leaves: every object whose word names one block has that block
+ *              rebuilt in place from its first k intact ids ascending, data
+ *              blocks clipped to `size`, bytes past `size` read as zero and
+ *              never touched; a clean object and a LEOEC_LOCATE_MANY object
+ *              are not written at all;
+ *   totals[0]  is the number of objects named and rebuilt, totals[1] the number
+ *              of LEOEC_LOCATE_MANY objects; both words are overwritten.
+ * Layout, alignment and stride rules are leoec_scrub_ws_dev's.
+ * Served:
+ *   (a) everything leoec_scrub_ws_dev serves (its classes (a) and (b)): the
+ *       call and the query are forwarded to it, with the same workspace size,
+ *       statuses and bytes; the bitmatrix configurations it refuses stay
+ *       refused;
+ *   (c) vandrs w = 16 / 32, and vandrs / isars w = 8 with k > 16 or m > 4, all
+ *       with m >= 2 and k + m <= 31: leoec_locate_gfw_dev's class (c) less
+ *       k + m = 32, where the bit of id 31 is LEOEC_LOCATE_MANY's own word,
+ *       the reason leoec_scrub_ws_dev gives.
+ * Everything else (m = 1, k + m >= 32, the bitmatrix configurations
+ * leoec_scrub_ws_dev refuses) is LEOEC_E_UNSUPPORTED, returned before the
+ * device is opened; invalid parameters keep their leoec_check_params status;
+ * nobj == 0 is LEOEC_OK with nothing written.  The checks come in
+ * leoec_scrub_ws_dev's order: layout and parameters, served, empty batch,
+ * pointers and strides, workspace, then the device.
+ * workspace for (c): leoec_scrub_ws_dev's layout: device, 16-byte aligned: a
+ * 16-byte header, then round_up(4 * nobj, 16) bytes of index words, then the
+ * encode region.  The query's size holds every object's m coding blocks (one
+ * pass); the call takes anything down to 16 + round_up(4 * nobj, 16) +
+ * m * block_size and then works in chunks of objects on the same stream, with
+ * the same results.  workspace_bytes below that minimum, report, totals or
+ * workspace NULL or misaligned (4, 4 and 16 bytes), or report or totals inside
+ * the workspace: LEOEC_E_ARG.  The workspace's contents after the call are
+ * unspecified.
+ * What runs for (c), per chunk, on `stream`: the class's encode into the
+ * workspace, a memset, leoec_locate_gfw_dev's launch, one launch that writes
+ * the final words, lists the objects that name a block and adds to the totals,
+ * and one launch of fixed size that rebuilds the listed objects' blocks on
+ * w-bit words from the code's block table (leoec_scrub_wrows).  Nothing is
+ * allocated, uploaded or waited for, so the call can be captured into a
+ * graph, after the first call: the first call of a code on a device builds
+ * that table on the host (k + m records, under 5 KB), uploads it with a
+ * blocking copy and loads the code objects (1-2 ms each); the leoec_gf_init
+ * warm-up does not cover them.  The table cache holds 16 tables per process
+ * and is its own, beside leoec_heal_dev's and leoec_scrub_ws_dev's; past that
+ * the call runs leoec_locate_gfw_dev then leoec_heal_dev's other path, which
+ * brings the masks back to the host (one stream synchronisation), rebuilds
+ * runs of consecutive objects with the same mask and fills the workspace's
+ * index words from the host.
+ * The limit at m = 2 is leoec_locate_dev's: with m >= 3 two damaged blocks are
+ * never taken for one, with m = 2 they may be reported as a third block, which
+ * is then "healed": the stripe is left consistent but wrong. */
+int leoec_scrub_gfw_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                        uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                        uint32_t *report, uint32_t *totals, void *workspace,
+                        uint64_t workspace_bytes, void *stream);
+
 /* ---- introspection ------------------------------------------------------ */
+
+/* The map leoec_scrub_gfw_dev rebuilds one lost block of an object of its
+ * class (c) with; needs no device.  surv[0..k): the first k ids ascending
+ * without `block`, leoec_decode_dev's survivors.  coef[0..k) (cap >= k words):
+ * the GF(2^w) coefficients that give `block` from the blocks surv[0..k) in
+ * that order, word by word: a record of the table the device holds, equal to
+ * leoec_heal_rows' surv and coef for the mask 1 << block.  A block outside
+ * 0..k+m-1: LEOEC_E_BAD_ID; surv or coef NULL or cap too small: LEOEC_E_ARG.
+ * Serves class (c) of leoec_scrub_gfw_dev only and gives its statuses
+ * otherwise; class (a) is LEOEC_E_UNSUPPORTED (those maps are leoec_heal_rows
+ * and leoec_scrub_bitrows). */
+int leoec_scrub_wrows(int coding, int k, int m, int w, int block, int *surv, uint32_t *coef,
+                      int cap);
 
 /* The map leoec_scrub_ws_dev rebuilds one lost block of a cauchyrs or
  * liberation object with; needs no device.  surv[0..k): the first k ids

@@ -47,6 +47,7 @@ EXPORTS = (
     "leoec_locate_ws_dev", "leoec_locate_bitrows", "leoec_scrub_dev_workspace", "leoec_scrub_dev",
     "leoec_scrub_ws_dev_workspace", "leoec_scrub_ws_dev", "leoec_scrub_bitrows",
     "leoec_locate_gfw_dev_workspace", "leoec_locate_gfw_dev", "leoec_locate_wrows",
+    "leoec_scrub_gfw_dev_workspace", "leoec_scrub_gfw_dev", "leoec_scrub_wrows",
 )
 
 
@@ -116,6 +117,10 @@ def _load(path=LIB_PATH):
     L.leoec_scrub_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
     L.leoec_scrub_bitrows.argtypes = [c_int] * 5 + [ctypes.POINTER(c_int),
                                                     ctypes.POINTER(ctypes.c_uint32), c_int]
+    L.leoec_scrub_gfw_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
+    L.leoec_scrub_gfw_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.leoec_scrub_wrows.argtypes = [c_int] * 5 + [ctypes.POINTER(c_int),
+                                                  ctypes.POINTER(ctypes.c_uint32), c_int]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

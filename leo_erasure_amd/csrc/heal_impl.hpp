@@ -57,6 +57,17 @@ __device__ __forceinline__ uint32_t heal_id(const uint32_t (&idw)[N], int x) {
   return __builtin_amdgcn_readfirstlane((idw[x >> 2] >> (8 * (x & 3))) & 0xFFu);
 }
 
+// The word at p, for a wave-uniform p that nothing writes while the kernel
+// runs (the list kernels of scrub.hip: the table; the list, its count and the
+// words, which an earlier launch on the stream wrote).  A kernel that stores
+// gets a vector load and a full vmcnt wait for a plain uniform load, since the
+// compiler cannot rule out that its own stores reach the word; the constant
+// address space says they do not.
+__device__ __forceinline__ uint32_t uniform_word(const uint32_t* p) {
+  typedef const uint32_t __attribute__((address_space(4))) const_word;
+  return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const_word*>(reinterpret_cast<uintptr_t>(p)));
+}
+
 // Block `id` of the object whose rows start at ob (objs) and pb (parity): a
 // data id is clipped to the object's size, a coding id is whole.  The id comes
 // from the record through readfirstlane (heal_id), so everything here is

@@ -125,7 +125,7 @@ struct Knobs {
                              //   (masks copied back, one plan launch per run of equal masks),
                              //   also where gf8_heal would serve
   // scrub.hip
-  int scrub_grid = 0;        // LEOEC_SCRUB_GRID=n: gf8_heal_list's and bit_heal_list's grid capped at n workgroups
+  int scrub_grid = 0;        // LEOEC_SCRUB_GRID=n: gf8_heal_list's, bit_heal_list's and gfw_heal_list's grid capped at n workgroups
                              //   (the persistent loop at test-sized batches; 0: the shipped grid)
 };
 

@@ -29,7 +29,8 @@
 // (locate_reset, locate_tail).
 // leoec_scrub_dev (scrub.hip) runs op_locate_dev with its own steps in it
 // (scrub_steps.hpp): its kernel stands in locate_finish's place;
-// leoec_scrub_ws_dev does the same with op_locate_ws_dev's bitmatrix branch.
+// leoec_scrub_ws_dev does the same with op_locate_ws_dev's bitmatrix branch,
+// leoec_scrub_gfw_dev with op_locate_gfw_dev's word branch.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
@@ -386,11 +387,16 @@ int gfw_locate_code(int coding, int k, int m, int w, const Code** c,
   return gfw_ratio(*c, ratio);
 }
 
+}  // namespace
+
 // Class (a) of leoec_locate_gfw_dev: what leoec_locate_ws_dev serves, and the
 // bitmatrix configurations it refuses, which stay refused.
+// (scrub_steps.hpp: scrub.hip asks too)
 bool gfw_forwarded(int coding, int k, int m, int w) {
   return bit_class(coding) || locate_served(coding, k, m, w);
 }
+
+namespace {
 
 int op_locate_wrows(int coding, int k, int m, int w, uint32_t* ratio, int cap) {
   int rc = check_params(coding, k, m, w);
@@ -423,9 +429,15 @@ int launch_gfw_locate(int w, const GfwLocArgs& a, uint64_t no, uint32_t* lost, h
   return launch_kernel(gfw_locate<32>, grid, block, 0, s, a, lost);
 }
 
+}  // namespace
+
+// steps (scrub_steps.hpp): leoec_scrub_gfw_dev's share of the word branch,
+// with `workspace` its encode region alone (the chunk size comes from
+// workspace_bytes); none for leoec_locate_gfw_dev itself.
 int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
                       uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
-                      uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
+                      uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s,
+                      LocateSteps* steps) {
   uint64_t bs;
   int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
   if (rc) return rc;
@@ -437,10 +449,12 @@ int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint
   if ((rc = gfw_locate_code(coding, k, m, w, &c, &ratio))) return rc;
   if (nobj == 0 || bs == 0) return LEOEC_OK;
   if (!lost || ((uintptr_t)lost & 3u)) return LEOEC_E_ARG;
+  if (steps && (rc = steps->check(bs))) return rc;
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   if ((rc = WsPass::check(workspace, workspace_bytes, m, bs))) return rc;
   if (ratio->size() > (size_t)kGfwLocWords) return LEOEC_E_UNSUPPORTED;  // (k + m <= 32: never)
   if ((rc = device_init())) return rc;
+  if (steps && (rc = steps->begin(*c, s))) return rc;
   WsPass pass;
   if ((rc = pass.prepare(*c, bs, size, objs, obj_stride, parity, parity_stride))) return rc;
   GfwLocArgs a;
@@ -459,12 +473,10 @@ int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint
     if (rc) return rc;
     a.parity = parity + o0 * parity_stride;
     if ((rc = launch_gfw_locate(w, a, no, lost + o0, s))) return rc;
-    return locate_tail(nullptr, lost, o0, no, s);
+    return locate_tail(steps, lost, o0, no, s);
   };
   return pass.run(workspace, workspace_bytes, nobj, a.tiles, s, chunk);
 }
-
-}  // namespace
 
 }  // namespace leoec
 
@@ -482,7 +494,7 @@ int leoec_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, u
   return leoec::guarded([&] {
     return leoec::op_locate_gfw_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
                                     parity_stride, lost, workspace, workspace_bytes,
-                                    (hipStream_t)stream);
+                                    (hipStream_t)stream, nullptr);
   });
 }
 

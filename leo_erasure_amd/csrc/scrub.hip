@@ -31,12 +31,26 @@
 // in a cache of their own; when it is full the call is the composition:
 // op_locate_ws_dev with scrub_finish counting only, then op_heal_dev's generic
 // path.
-// Both calls are one function, scrub_run: one ScrubSteps in the locate call,
-// which differs between them in the encode bytes of its workspace check, the
-// table it asks for and the heal-list kernel it launches.
+//
+// leoec_scrub_gfw_dev adds the GF(2^w) word classes in the same way (vandrs
+// w = 16 / 32; vandrs / isars w = 8 with k > 16 or m > 4; m >= 2, k + m <= 31)
+// and forwards everything else to leoec_scrub_ws_dev.  Per chunk:
+//   locate          op_locate_gfw_dev's encode, memset and gfw_locate;
+//   scrub_finish    as above;
+//   gfw_heal_list   (scrub_gfw_impl.hpp) one named block of every listed
+//                   object from the code's block table (scrub_gfw_table.hpp),
+//                   from a fixed grid.
+// Workspace and table cache as leoec_scrub_ws_dev's (a cache of its own, under
+// 5 KB a table); when it is full the call is op_locate_gfw_dev with
+// scrub_finish counting only, then op_heal_dev's generic path.
+// All three calls are one function, scrub_run: one ScrubSteps in the locate
+// call, which differs between them (ScrubKind) in the encode bytes of its
+// workspace check, the table it asks for and the heal-list kernel it launches.
 // This unit is kept out of engine.cpp / capi.cpp for verify.hip's reason: the
 // host sanitizer harness links those against stand-in kernels.  The gf_init
 // warm-up does not load this unit's kernels either.
+#include <map>
+#include <mutex>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -45,6 +59,7 @@
 #include "engine.hpp"
 #include "knobs.hpp"
 #include "scrub_bit_impl.hpp"
+#include "scrub_gfw_impl.hpp"
 #include "scrub_impl.hpp"
 #include "scrub_steps.hpp"
 #include "ws_pass.hpp"
@@ -81,8 +96,8 @@ scrub_finish(uint32_t* __restrict__ words, uint32_t n, uint32_t* __restrict__ li
   const uint32_t f = v == 0xFFFFFFFFu ? 0u : (v != 0u && (v & (v - 1u)) == 0u) ? v : LEOEC_LOCATE_MANY;
   if (in) words[i] = f;
   // (no single-bit word is LEOEC_LOCATE_MANY's own bit: k + m <= 20 for
-  // leoec_scrub_dev, <= 31 for leoec_scrub_ws_dev, which refuses k + m = 32
-  // for this line's sake)
+  // leoec_scrub_dev, <= 31 for leoec_scrub_ws_dev and leoec_scrub_gfw_dev,
+  // which refuse k + m = 32 for this line's sake)
   const bool many = f == LEOEC_LOCATE_MANY;
   const bool one = f != 0u && !many;
   const uint64_t b1 = __builtin_amdgcn_ballot_w64(one);
@@ -184,13 +199,84 @@ int op_scrub_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, ui
 }
 
 // ---------------------------------------------------------------------------
-// Both calls.
+// The GF(2^w) word classes: leoec_scrub_gfw_dev.
+
+// A configuration of class (c): leoec_locate_gfw_dev's statuses (an empty
+// batch with no buffers goes through its layout, parameter and served tests
+// and ends there: no device), then k + m = 32, for bit_scrub_served's reason.
+int gfw_scrub_served(int coding, int k, int m, int w, uint64_t size) {
+  const int rc = op_locate_gfw_dev(coding, k, m, w, nullptr, 0, size, 0, nullptr, 0, nullptr,
+                                   nullptr, 0, nullptr, nullptr);
+  if (rc) return rc;
+  return scrub_gfw_shape(k, m);
+}
+
+// The host image of a code's block table, built once and kept with the cached
+// Code (get_code never frees one); needs no device.  The device gets a copy of
+// it (scrub_gfw_table), leoec_scrub_wrows reads its records.
+int scrub_gfw_image(const Code* c, const std::vector<uint32_t>** out) {
+  struct Entry {
+    int rc;
+    std::vector<uint32_t> image;
+  };
+  static std::mutex mu;
+  static std::map<const Code*, Entry> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(c);
+  if (it == cache.end()) {
+    Entry e;
+    const auto rows = [c](const int* surv, int block, std::vector<uint32_t>* r) {
+      return gf_rows(*c, surv, &block, 1, r);
+    };
+    e.rc = scrub_gfw_build_table(c->k, c->m, rows, &e.image);
+    it = cache.emplace(c, std::move(e)).first;
+  }
+  *out = &it->second.image;
+  return it->second.rc;
+}
+
+// The block table of the code on the current device (dev_table.hpp), one per
+// (coding, k, m, w, device), in a cache of its own: nullptr when it is full,
+// and the caller runs the composition.
+int scrub_gfw_table(const Code& c, const uint32_t** out) {
+  // at most 16 x 5 KB of device memory; leaked: never destroyed at exit
+  static auto* const cache = new DevTableCache<std::tuple<int, int, int, int>, 16>;
+  const auto build = [&](std::vector<uint32_t>* host) {
+    const std::vector<uint32_t>* image;
+    const int rc = scrub_gfw_image(&c, &image);
+    if (!rc) *host = *image;
+    return rc;
+  };
+  return cache->get(std::make_tuple(c.coding, c.k, c.m, c.w), build, out);
+}
+
+int op_scrub_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                               uint64_t* bytes) {
+  if (gfw_forwarded(coding, k, m, w))  // its own statuses, layout and parameters first
+    return op_scrub_ws_dev_workspace(coding, k, m, w, size, nobj, bytes);
+  uint64_t bs = 0;
+  int rc = op_layout(coding, k, m, w, size, &bs, nullptr);
+  if (rc) return rc;
+  if ((rc = gfw_scrub_served(coding, k, m, w, size))) return rc;
+  if (!bytes) return LEOEC_E_ARG;
+  uint64_t enc;
+  if (!encode_region_bytes(m, bs, nobj, &enc)) return LEOEC_E_BAD_SIZE;
+  return scrub_ws_workspace(nobj, enc, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
+}
+
+// ---------------------------------------------------------------------------
+// All three calls.
+
+// The kernel family of a scrub call: leoec_scrub_dev's fused GF(2^8) classes,
+// leoec_scrub_ws_dev's bitmatrix classes, leoec_scrub_gfw_dev's word classes.
+enum class ScrubKind { gf8, bit, gfw };
 
 // The scrub calls' share of the locate call they run (scrub_steps.hpp):
-// leoec_scrub_dev's of op_locate_dev, and with `bit` leoec_scrub_ws_dev's of
-// op_locate_ws_dev's bitmatrix branch.
+// leoec_scrub_dev's of op_locate_dev, leoec_scrub_ws_dev's of
+// op_locate_ws_dev's bitmatrix branch and leoec_scrub_gfw_dev's of
+// op_locate_gfw_dev's word branch.
 struct ScrubSteps final : LocateSteps {
-  bool bit = false;
+  ScrubKind kind = ScrubKind::gf8;
   int k = 0, m = 0, w = 0;
   uint8_t* objs = nullptr;
   uint64_t obj_stride = 0, size = 0, bs = 0, nobj = 0;
@@ -201,8 +287,8 @@ struct ScrubSteps final : LocateSteps {
   void* workspace = nullptr;
   uint64_t workspace_bytes = 0;
   bool begun = false;               // begin() ran: the device is open
-  const uint32_t* table = nullptr;  // heal's, bit: the block table; nullptr after begin(): cache full
-  HealListFn heal = nullptr;        // !bit
+  const uint32_t* table = nullptr;  // heal's; bit, gfw: the block table; nullptr after begin(): cache full
+  HealListFn heal = nullptr;        // gf8
 
   uint32_t* header() const { return static_cast<uint32_t*>(workspace); }
   uint32_t* list() const { return header() + kScrubHeader / sizeof(uint32_t); }
@@ -211,8 +297,9 @@ struct ScrubSteps final : LocateSteps {
     bs = block_size;
     if (!totals || ((uintptr_t)totals & 3u)) return LEOEC_E_ARG;
     if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
-    uint64_t enc = 0, need;  // the header and the index words; bit: and one object's encode
-    if ((bit && !encode_region_bytes(m, bs, 1, &enc)) || !scrub_ws_workspace(nobj, enc, &need))
+    uint64_t enc = 0, need;  // the header and the index words; bit, gfw: and one object's encode
+    if ((kind != ScrubKind::gf8 && !encode_region_bytes(m, bs, 1, &enc)) ||
+        !scrub_ws_workspace(nobj, enc, &need))
       return LEOEC_E_BAD_SIZE;
     if (workspace_bytes < need) return LEOEC_E_ARG;
     if (overlaps(report, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
@@ -222,10 +309,12 @@ struct ScrubSteps final : LocateSteps {
   }
 
   int begin(const Code& c, hipStream_t s) override {
-    const int rc = bit ? scrub_bit_table(c, &table) : heal_table(c, &table);
+    const int rc = kind == ScrubKind::bit   ? scrub_bit_table(c, &table)
+                   : kind == ScrubKind::gfw ? scrub_gfw_table(c, &table)
+                                            : heal_table(c, &table);
     if (rc) return rc;
     begun = true;
-    if (!bit) heal = gf8_heal_list_pick(std::make_index_sequence<kMaxK>{}, k);
+    if (kind == ScrubKind::gf8) heal = gf8_heal_list_pick(std::make_index_sequence<kMaxK>{}, k);
     return hipMemsetAsync(totals, 0, 2 * sizeof(uint32_t), s) == hipSuccess ? LEOEC_OK : LEOEC_E_HIP;
   }
 
@@ -247,13 +336,21 @@ struct ScrubSteps final : LocateSteps {
     h.unhealed = nullptr;
     h.table = table;
     h.size = size;
-    h.bs = (uint32_t)bs;  // < 2^32 (check_dev_batch); bit: a multiple of 16 w
+    h.bs = (uint32_t)bs;  // < 2^32 (check_dev_batch); bit, gfw: a multiple of 16 w
     h.k = (uint32_t)k;
     h.m = (uint32_t)m;
     h.nobj = (uint32_t)no;
     h.tiles = h.tmap = h.tperm = 0;  // the launcher's
     const uint32_t cap = kMeasureBuild && knobs().scrub_grid > 0 ? (uint32_t)knobs().scrub_grid : 0u;
-    if (!bit) return heal(h, list(), header(), cap, s);
+    if (kind == ScrubKind::gf8) return heal(h, list(), header(), cap, s);
+    if (kind == ScrubKind::gfw) {
+      GfwHealArgs g;
+      g.h = h;
+      g.h.tiles = (uint32_t)((bs + kGfwHealTile - 1) / kGfwHealTile);  // gfw_locate's: no x tiles < 2^31
+      g.rec_words = scrub_gfw_record_words(k);
+      g.red = field(8).mul(0x80u, 2u);  // alpha^8 reduced: the polynomial's low byte
+      return launch_gfw_heal_list(w, g, list(), header(), cap, s);
+    }
     BitHealArgs a;
     a.h = h;
     a.w = (uint32_t)w;
@@ -265,14 +362,14 @@ struct ScrubSteps final : LocateSteps {
   }
 };
 
-// Both calls after their own served tests: the locate call with the steps in
-// it, then, when the table cache was full, leoec_heal_dev's generic path.
-int scrub_run(bool bit, int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+// The three calls after their own served tests: the locate call with the steps
+// in it, then, when the table cache was full, leoec_heal_dev's generic path.
+int scrub_run(ScrubKind kind, int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
               uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
               uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
               hipStream_t s) {
   ScrubSteps st;
-  st.bit = bit;
+  st.kind = kind;
   st.k = k;
   st.m = m;
   st.w = w;
@@ -286,19 +383,23 @@ int scrub_run(bool bit, int coding, int k, int m, int w, uint8_t* objs, uint64_t
   st.totals = totals;
   st.workspace = workspace;
   st.workspace_bytes = workspace_bytes;
-  // bit: the encode region behind the header and the index words (check()
+  // bit, gfw: the encode region behind the header and the index words (check()
   // refuses a workspace that has none before anything looks at it)
   uint64_t head;
   void* enc = nullptr;
   uint64_t enc_bytes = 0;
-  if (bit && workspace && scrub_workspace(nobj, &head) && workspace_bytes > head) {
+  if (kind != ScrubKind::gf8 && workspace && scrub_workspace(nobj, &head) && workspace_bytes > head) {
     enc = static_cast<uint8_t*>(workspace) + head;
     enc_bytes = workspace_bytes - head;
   }
-  const int rc = bit ? op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
-                                        parity_stride, report, enc, enc_bytes, s, &st)
-                     : op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
-                                     parity_stride, report, s, &st);
+  const int rc =
+      kind == ScrubKind::bit   ? op_locate_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                                  parity_stride, report, enc, enc_bytes, s, &st)
+      : kind == ScrubKind::gfw ? op_locate_gfw_dev(coding, k, m, w, objs, obj_stride, size, nobj,
+                                                   parity, parity_stride, report, enc, enc_bytes, s,
+                                                   &st)
+                               : op_locate_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                               parity_stride, report, s, &st);
   if (rc || !st.begun || st.table) return rc;
   // the table cache is full: the words are final and counted; the rest is
   // leoec_heal_dev's generic path (one synchronisation)
@@ -309,7 +410,7 @@ int scrub_run(bool bit, int coding, int k, int m, int w, uint8_t* objs, uint64_t
 int op_scrub_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride, uint64_t size,
                  uint64_t nobj, uint8_t* parity, uint64_t parity_stride, uint32_t* report,
                  uint32_t* totals, void* workspace, uint64_t workspace_bytes, hipStream_t s) {
-  return scrub_run(false, coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+  return scrub_run(ScrubKind::gf8, coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
                    report, totals, workspace, workspace_bytes, s);
 }
 
@@ -322,8 +423,35 @@ int op_scrub_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj
                         totals, workspace, workspace_bytes, s);
   const int rc = bit_scrub_served(coding, k, m, w, size);
   if (rc) return rc;
-  return scrub_run(true, coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride, report,
-                   totals, workspace, workspace_bytes, s);
+  return scrub_run(ScrubKind::bit, coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                   parity_stride, report, totals, workspace, workspace_bytes, s);
+}
+
+int op_scrub_gfw_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                     uint32_t* report, uint32_t* totals, void* workspace, uint64_t workspace_bytes,
+                     hipStream_t s) {
+  if (gfw_forwarded(coding, k, m, w))  // served or LEOEC_E_UNSUPPORTED there
+    return op_scrub_ws_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity, parity_stride,
+                           report, totals, workspace, workspace_bytes, s);
+  const int rc = gfw_scrub_served(coding, k, m, w, size);
+  if (rc) return rc;
+  return scrub_run(ScrubKind::gfw, coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                   parity_stride, report, totals, workspace, workspace_bytes, s);
+}
+
+int op_scrub_wrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* coef, int cap) {
+  int rc = check_params(coding, k, m, w);
+  if (rc) return rc;
+  if (gfw_forwarded(coding, k, m, w)) return LEOEC_E_UNSUPPORTED;
+  if ((rc = gfw_scrub_served(coding, k, m, w, 0))) return rc;
+  if (block < 0 || block >= k + m) return LEOEC_E_BAD_ID;
+  if (!surv || !coef || cap < k) return LEOEC_E_ARG;
+  const Code* c;
+  if ((rc = get_code(coding, k, m, w, &c))) return rc;
+  const std::vector<uint32_t>* image;
+  if ((rc = scrub_gfw_image(c, &image))) return rc;
+  return scrub_gfw_record(*image, k, m, block, surv, coef);
 }
 
 int op_scrub_bitrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* rows,
@@ -390,6 +518,29 @@ int leoec_scrub_bitrows(int coding, int k, int m, int w, int block, int* surv, u
                         int cap) {
   return leoec::guarded(
       [&] { return leoec::op_scrub_bitrows(coding, k, m, w, block, surv, rows, cap); });
+}
+
+int leoec_scrub_gfw_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                  uint64_t* bytes) {
+  return leoec::guarded(
+      [&] { return leoec::op_scrub_gfw_dev_workspace(coding, k, m, w, size, nobj, bytes); });
+}
+
+int leoec_scrub_gfw_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
+                        uint64_t size, uint64_t nobj, uint8_t* parity, uint64_t parity_stride,
+                        uint32_t* report, uint32_t* totals, void* workspace,
+                        uint64_t workspace_bytes, void* stream) {
+  return leoec::guarded([&] {
+    return leoec::op_scrub_gfw_dev(coding, k, m, w, objs, obj_stride, size, nobj, parity,
+                                   parity_stride, report, totals, workspace, workspace_bytes,
+                                   (hipStream_t)stream);
+  });
+}
+
+int leoec_scrub_wrows(int coding, int k, int m, int w, int block, int* surv, uint32_t* coef,
+                      int cap) {
+  return leoec::guarded(
+      [&] { return leoec::op_scrub_wrows(coding, k, m, w, block, surv, coef, cap); });
 }
 
 }  // extern "C"

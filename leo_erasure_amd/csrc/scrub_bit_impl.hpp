@@ -55,16 +55,6 @@ struct BitHealArgs {
   uint32_t pad;
 };
 
-// The word at p, for a wave-uniform p that nothing writes while the kernel
-// runs (the table; the list, its count and the words, which an earlier launch
-// on the stream wrote).  A kernel that stores gets a vector load and a full
-// vmcnt wait for a plain uniform load, since the compiler cannot rule out that
-// its own stores reach the word; the constant address space says they do not.
-__device__ __forceinline__ uint32_t uniform_word(const uint32_t* p) {
-  typedef const uint32_t __attribute__((address_space(4))) const_word;
-  return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const_word*>(reinterpret_cast<uintptr_t>(p)));
-}
-
 // list: indices into the chunk, *count of them, both written by an earlier
 // launch on the stream.  count x tiles <= nobj x tiles < 2^31.
 __global__ void __launch_bounds__(kBitHealLanes)

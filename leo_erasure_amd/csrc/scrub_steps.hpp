@@ -45,6 +45,21 @@ int op_locate_ws_dev(int coding, int k, int m, int w, const uint8_t* objs, uint6
                      uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s,
                      LocateSteps* steps);
 
+// locate.hip: class (a) of leoec_locate_gfw_dev, what it forwards to
+// leoec_locate_ws_dev (the bitmatrix configurations that call refuses among
+// them).
+bool gfw_forwarded(int coding, int k, int m, int w);
+
+// locate.hip; steps == nullptr: leoec_locate_gfw_dev.  The steps stand in the
+// word branch (class (c)) at the same three places as in op_locate_ws_dev:
+// check after the served test, the empty batch and `lost`'s check, begin once
+// the device is open, finish(o0, no, s) in locate_finish's place after the
+// chunk's encode, memset and gfw_locate.  `workspace` is the encode region.
+int op_locate_gfw_dev(int coding, int k, int m, int w, const uint8_t* objs, uint64_t obj_stride,
+                      uint64_t size, uint64_t nobj, const uint8_t* parity, uint64_t parity_stride,
+                      uint32_t* lost, void* workspace, uint64_t workspace_bytes, hipStream_t s,
+                      LocateSteps* steps);
+
 // heal.hip: leoec_heal_dev, and the code's pattern table on the current
 // device: LEOEC_OK and *out = the device image, or *out = nullptr when the
 // cache is full; a status when the build or the upload failed.

@@ -389,6 +389,67 @@ def scrub_bitrows(coding, params, block):
     return list(surv[:k]), [list(rows[r * rw:(r + 1) * rw]) for r in range(w)]
 
 
+def scrub_gfw_workspace(coding, params, size, nobj):
+    """leoec_scrub_gfw_dev_workspace: bytes of workspace scrub_gfw() wants for
+    one pass over the batch: scrub_ws_workspace()'s for everything scrub_ws()
+    serves; for the GF(2^w) word classes the header, one index word per object
+    and the encode region of ``nobj`` objects."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_scrub_gfw_dev_workspace(_cid(coding), k, m, w, size, nobj,
+                                                 ctypes.byref(out)))
+    return out.value
+
+
+def scrub_gfw(coding, params, objs, size, parity, nobj=None, report=None, totals=None,
+              workspace=None, stream=None):
+    """leoec_scrub_gfw_dev: scrub_ws(), also for the GF(2^w) word classes
+    (vandrs w = 16 / 32 and vandrs / isars w = 8 with k > 16 or m > 4; m >= 2,
+    k + m <= 31): locate_gfw() then heal() in one call.  Returns ``(report,
+    totals)`` as scrub() does.  ``workspace`` (uint8) follows scrub_ws()'s
+    rules: allocated when not given, its encode region up to
+    ``VERIFY_WORKSPACE_CAP`` (a smaller workspace than ``scrub_gfw_workspace()``
+    gives the same results in more chunks of objects), and required on an
+    explicit ``stream``."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    if report is None:
+        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    if totals is None:
+        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
+    _words(report, nobj, "report")
+    _words(totals, 2, "totals")
+    need = scrub_gfw_workspace(coding, params, size, nobj)
+    if workspace is None:
+        head = 16 + (4 * nobj + 15) // 16 * 16
+        if stream is not None:
+            raise ValueError("scrub_gfw on an explicit stream needs an explicit workspace "
+                             f"({need} B for one pass)")
+        enc = need - head  # 0 for everything scrub() serves
+        if enc:
+            enc = max(min(enc, VERIFY_WORKSPACE_CAP), m * bs)
+        workspace = torch.empty(head + enc, dtype=torch.uint8, device=objs.device)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    _lib.check(lib.leoec_scrub_gfw_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
+                                       size, nobj, parity.data_ptr(), _row_stride(parity),
+                                       report.data_ptr(), totals.data_ptr(), workspace.data_ptr(),
+                                       workspace.numel(), _stream(stream)))
+    return report, totals
+
+
+def scrub_wrows(coding, params, block):
+    """leoec_scrub_wrows (no device needed): the map scrub_gfw() rebuilds block
+    ``block`` of an object of the GF(2^w) word classes with.  Returns ``(surv,
+    coef)``: the k survivor ids (the first k ids ascending without ``block``)
+    and the k GF(2^w) coefficients that give ``block`` from those survivors in
+    that order."""
+    k, m, w = params
+    surv = (ctypes.c_int * max(k, 1))()
+    coef = (ctypes.c_uint32 * max(k, 1))()
+    _lib.check(lib.leoec_scrub_wrows(_cid(coding), k, m, w, block, surv, coef, max(k, 1)))
+    return list(surv[:k]), list(coef[:k])
+
+
 def locate_bitrows(coding, params):
     """leoec_locate_bitrows (no device needed): the GF(2) ratios locate_ws()
     tests the syndromes of cauchyrs and liberation with: ``m - 1`` lists of k
