@@ -229,6 +229,85 @@ int leoec_heal_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_
                    uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
                    const uint32_t *lost, uint32_t *unhealed, void *stream);
 
+/* Workspace bytes leoec_heal_ws_dev needs for this batch: leoec_scrub_dev's
+ * layout, 16 + round_up(4 * nobj, 16); LEOEC_E_BAD_SIZE when that overflows;
+ * bytes == NULL: LEOEC_E_ARG, checked after the served checks.  Configurations
+ * leoec_heal_ws_dev does not serve, and invalid ones, get its statuses.  Needs
+ * no device. */
+int leoec_heal_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,
+                                uint64_t *bytes);
+
+/* leoec_heal_dev with a workspace: every class it serves rebuilt with the
+ * caller's masks without a host round trip.  The result is leoec_heal_dev's
+ * byte for byte: layout, alignment and stride rules, the meaning of lost, the
+ * survivors (the first k intact ids ascending), the clipping of data blocks
+ * to `size` (bytes past it are never touched), unhealed (0 for a healed or
+ * clean object, lost[o] for one with more than m bits or a bit at or above
+ * k + m, of which nothing is written; every word overwritten), lost never
+ * written, lost == unhealed LEOEC_E_ARG.  An object with lost[o] == 0 is
+ * untouched.  At k + m = 32 bit 31 is block 31 like any other: no word of
+ * this call is LEOEC_LOCATE_MANY.
+ * totals: device, 4-byte aligned, 2 words, both overwritten: totals[0] the
+ * number of objects rebuilt, totals[1] the number of unrecoverable ones.
+ * workspace: device, 16-byte aligned, at least leoec_heal_ws_dev_workspace's
+ * bytes (a 16-byte header and one index word per object); its contents after
+ * the call are unspecified.  lost, unhealed, totals or workspace NULL or
+ * misaligned, unhealed, totals or lost inside the workspace, or
+ * workspace_bytes below the query's: LEOEC_E_ARG.
+ * Served: every class leoec_heal_dev serves (k + m <= 32, m = 1 included)
+ * whose pattern table, one record per mask of 1..m lost ids, is at most
+ * 8 MiB:
+ *   vandrs w = 8 and isars with k <= 16, m <= 4: always (leoec_heal_dev's own
+ *     table, 8 MB at (16,4));
+ *   any other code: 4 * (1104 + R * (8 + m * k * c)) <= 8 * 2^20 with
+ *     R = C(k+m, 1) + ... + C(k+m, m) and c = 1 for vandrs and isars, c = w
+ *     for cauchyrs and liberation.  vandrs(20,4,8) (4.6 MB), cauchyrs(10,4,8)
+ *     (1.9 MB) and every k + m = 32, m = 2 code are served; vandrs(16,15,8)
+ *     (2^31 masks) is not.
+ * Everything else is LEOEC_E_UNSUPPORTED from the call and the query,
+ * returned before the device is opened: such a batch goes to leoec_heal_dev.
+ * Invalid parameters keep their leoec_check_params status; nobj == 0 (and
+ * size == 0, an object without blocks, as in leoec_heal_dev) is LEOEC_OK with
+ * nothing written.  The checks come in the scrub calls' order: layout and
+ * parameters, served, empty batch, pointers and strides, workspace, then the
+ * device.
+ * What runs on `stream`, per chunk of objects (a chunk only keeps a launch's
+ * item count below 2^31: one chunk for any batch a device holds): a one-wave
+ * launch that zeroes the list's count in the workspace's header (and, ahead
+ * of the first chunk, the totals; a launch, not a memset: DESIGN.md says why),
+ * one launch that writes unhealed, lists the objects to rebuild and adds to
+ * the totals, and one launch of fixed size over that list that rebuilds one
+ * lost block per item, so the survivors of an object are read once per lost
+ * block (the fused family: once per object).  Nothing
+ * is allocated, uploaded or waited for, so the call can be captured into a
+ * graph, after the first call: the first call of a code builds its table on
+ * the host (kept for the process's life; measured on one core of the build
+ * machine's CPU for the three largest images met: 0.40 s for cauchyrs(10,4,32),
+ * 7.6 MB, 1,470 inversions of 320 x 320 bit matrices; 0.12 s for vandrs(22,4,8),
+ * 6.9 MB; 0.08 s for vandrs(20,4,8), 4.6 MB; a small table with large blocks
+ * can take longer, liberation(29,2,29), 3.4 MB, 0.57 s for 496 inversions of
+ * 841 x 841), the first call of a code on a device uploads it with a
+ * blocking copy and loads the code objects (1-2 ms each); the leoec_gf_init
+ * warm-up covers neither.  The table cache holds 16 tables per process and is
+ * its own, beside leoec_heal_dev's (which the fused family shares with that
+ * call) and the scrub calls'; past that the call counts the totals and writes
+ * unhealed with one launch per chunk and then runs leoec_heal_dev's own path,
+ * which synchronises the stream once.  The thread's sticky HIP error is
+ * handled as by every *_dev call.
+ * Cost: by the number of damaged objects, not by the batch.  Measured on an
+ * MI355X, 2,048 objects of 1 MiB (Heal, "The workspace form"): a
+ * clean batch 0.020 ms in every class, 0.50-0.55 of leoec_heal_dev's; 32
+ * objects with two lost blocks each 0.020-0.064 ms net, 0.035-0.28 of
+ * leoec_heal_dev's.  A dense batch loses to leoec_heal_dev's one launch per run
+ * of equal masks, because every lost block rereads the survivors: with every
+ * object damaged 1.1x for vandrs w = 8 / isars with k <= 16, m <= 4, 2.1-3.2x
+ * with two lost blocks and 3.4-5.2x with four for the other classes.  A batch
+ * with one common mask belongs to leoec_heal_dev / leoec_decode_dev. */
+int leoec_heal_ws_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                      uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                      const uint32_t *lost, uint32_t *unhealed, uint32_t *totals, void *workspace,
+                      uint64_t workspace_bytes, void *stream);
+
 /* leoec_locate_dev's word for an object that is inconsistent in a way no
  * single block explains.  The bit lies at or above k + m, so leoec_heal_dev
  * takes the object for unrecoverable. */
@@ -594,6 +673,33 @@ int leoec_scrub_wrows(int coding, int k, int m, int w, int block, int *surv, uin
  * leoec_heal_rows). */
 int leoec_scrub_bitrows(int coding, int k, int m, int w, int block, int *surv, uint32_t *rows,
                         int cap);
+
+/* leoec_scrub_bitrows for a mask: the map leoec_heal_ws_dev rebuilds the r-th
+ * lost id (ascending, r from 0) of lost_mask of a cauchyrs or liberation
+ * object with, read from the table the device holds; needs no device.
+ * surv[0..k): the first k intact ids ascending; rows: leoec_scrub_bitrows'
+ * format (cap >= w * ceil(k*w / 32) words).  For a mask of one bit surv and
+ * rows are leoec_scrub_bitrows' for that block.  A bit at or above k + m:
+ * LEOEC_E_BAD_ID; more than m bits: LEOEC_E_NOT_ENOUGH_BLOCKS (leoec_heal_rows'
+ * statuses); r outside the mask's bit count, surv or rows NULL or cap too
+ * small: LEOEC_E_ARG.  Serves the cauchyrs and liberation codes
+ * leoec_heal_ws_dev serves and gives its statuses otherwise; vandrs and isars
+ * are LEOEC_E_UNSUPPORTED (their map is leoec_heal_rows). */
+int leoec_heal_bitrows(int coding, int k, int m, int w, uint32_t lost_mask, int r, int *surv,
+                       uint32_t *rows, int cap);
+
+/* leoec_scrub_wrows for a mask: the map leoec_heal_ws_dev rebuilds the r-th
+ * lost id (ascending, r from 0) of lost_mask with for a vandrs or isars code
+ * outside leoec_heal_dev's fused family (w = 16 / 32, w = 8 with k > 16 or
+ * m > 4), read from the table the device holds; needs no device.
+ * surv[0..k): the first k intact ids ascending; coef[0..k) (cap >= k words):
+ * the GF(2^w) coefficients that give the lost block from those survivors,
+ * equal to leoec_heal_rows' surv and row r of its coef for the same mask.
+ * Statuses as leoec_heal_bitrows'; cauchyrs, liberation and the fused family
+ * are LEOEC_E_UNSUPPORTED (their maps are leoec_heal_bitrows and
+ * leoec_heal_rows). */
+int leoec_heal_wrows(int coding, int k, int m, int w, uint32_t lost_mask, int r, int *surv,
+                     uint32_t *coef, int cap);
 
 /* The GF(2) ratios leoec_locate_ws_dev tests the syndromes of cauchyrs and
  * liberation with; needs no device.  rows (cap >= (m-1) * k * w words): word

@@ -118,6 +118,7 @@ const Knobs* read_env() {
   k->verify_form = env_int("LEOEC_VERIFY_FORM", k->verify_form);
   k->heal_form = env_int("LEOEC_HEAL_FORM", k->heal_form);
   k->scrub_grid = env_int("LEOEC_SCRUB_GRID", k->scrub_grid);
+  k->heal_ws_chunk = env_int("LEOEC_HEAL_WS_CHUNK", k->heal_ws_chunk);
   return k;
 }
 

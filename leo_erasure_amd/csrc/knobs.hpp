@@ -126,7 +126,12 @@ struct Knobs {
                              //   also where gf8_heal would serve
   // scrub.hip
   int scrub_grid = 0;        // LEOEC_SCRUB_GRID=n: gf8_heal_list's, bit_heal_list's and gfw_heal_list's grid capped at n workgroups
-                             //   (the persistent loop at test-sized batches; 0: the shipped grid)
+                             //   (the persistent loop at test-sized batches; 0: the shipped grid);
+                             //   heal_ws.hip's gfw_heal_masks and bit_heal_masks as well
+  // heal_ws.hip
+  int heal_ws_chunk = 0;     // LEOEC_HEAL_WS_CHUNK=n: leoec_heal_ws_dev in chunks of at most n objects
+                             //   (the chunk seam at test-sized batches; 0: the shipped chunk, which
+                             //   only keeps a launch's item count below 2^31)
 };
 
 const Knobs& knobs();

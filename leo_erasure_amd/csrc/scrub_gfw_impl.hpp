@@ -216,6 +216,10 @@ inline uint32_t gfw_heal_list_resident() { return 4u * (uint32_t)kGfwHealWaves; 
 // The fixed grid over the objects a describes (a.h.nobj and a.h.tiles are the
 // caller's): min(objects x tiles, resident workgroups of the device), at most
 // `cap` workgroups when cap is not 0 (LEOEC_SCRUB_GRID, measurement build).
+// (Left out where LEOEC_GFW_HEAL_LIST_NO_LAUNCH is defined: heal_ws_impl.hpp
+// takes this header's lane helpers, and a unit that sees the launcher gets the
+// three kernel instances it names.)
+#ifndef LEOEC_GFW_HEAL_LIST_NO_LAUNCH
 inline int launch_gfw_heal_list(int w, const GfwHealArgs& a, const uint32_t* list,
                                 const uint32_t* count, uint32_t cap, hipStream_t s) {
   const uint64_t all = (uint64_t)a.h.nobj * a.h.tiles;
@@ -227,6 +231,7 @@ inline int launch_gfw_heal_list(int w, const GfwHealArgs& a, const uint32_t* lis
   if (w == 16) return launch_kernel(gfw_heal_list<16>, g, b, 0, s, a, list, count);
   return launch_kernel(gfw_heal_list<32>, g, b, 0, s, a, list, count);
 }
+#endif
 
 }  // namespace detail
 }  // namespace leoec

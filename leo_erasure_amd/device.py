@@ -450,6 +450,77 @@ def scrub_wrows(coding, params, block):
     return list(surv[:k]), list(coef[:k])
 
 
+def heal_ws_workspace(coding, params, size, nobj):
+    """leoec_heal_ws_dev_workspace: bytes of workspace heal_ws() needs for
+    ``nobj`` objects (a 16-byte header and one index word per object)."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(lib.leoec_heal_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
+                                               ctypes.byref(out)))
+    return out.value
+
+
+def heal_ws(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, totals=None,
+            workspace=None, stream=None):
+    """leoec_heal_ws_dev: heal()'s bytes and ``unhealed`` for every class whose
+    pattern table is at most 8 MiB, without a host round trip and at a cost
+    that follows the number of damaged objects.  Returns ``(unhealed,
+    totals)``: ``totals`` (int32, 2 words) holds the number of objects rebuilt
+    and the number of unrecoverable ones.  ``unhealed``, ``totals`` and
+    ``workspace`` (uint8, at least ``heal_ws_workspace()`` bytes) are allocated
+    when not given; a call on an explicit ``stream`` must be given the
+    workspace, for verify()'s reason."""
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
+    if unhealed is None:
+        unhealed = torch.empty(nobj, dtype=torch.int32, device=objs.device)
+    if totals is None:
+        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
+    _words(lost, nobj, "lost")
+    _words(unhealed, nobj, "unhealed")
+    _words(totals, 2, "totals")
+    need = heal_ws_workspace(coding, params, size, nobj)
+    if workspace is None:
+        if stream is not None:
+            raise ValueError(f"heal_ws on an explicit stream needs an explicit workspace ({need} B)")
+        workspace = torch.empty(need, dtype=torch.uint8, device=objs.device)
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    _lib.check(lib.leoec_heal_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
+                                     size, nobj, parity.data_ptr(), _row_stride(parity),
+                                     lost.data_ptr(), unhealed.data_ptr(), totals.data_ptr(),
+                                     workspace.data_ptr(), workspace.numel(), _stream(stream)))
+    return unhealed, totals
+
+
+def heal_bitrows(coding, params, mask, r):
+    """leoec_heal_bitrows (no device needed): the map heal_ws() rebuilds the
+    r-th lost id (ascending, from 0) of ``mask`` of a cauchyrs or liberation
+    object with.  Returns ``(surv, rows)`` in scrub_bitrows()'s format: the k
+    survivor ids (the first k intact ids ascending) and w lists of
+    ``ceil(k w / 32)`` words, bit ``i w + c`` of row t set iff packet c of
+    block ``surv[i]`` feeds packet t of the lost block."""
+    k, m, w = params
+    rw = (k * w + 31) // 32
+    cap = max(w * rw, 1)
+    surv = (ctypes.c_int * max(k, 1))()
+    rows = (ctypes.c_uint32 * cap)()
+    _lib.check(lib.leoec_heal_bitrows(_cid(coding), k, m, w, mask, r, surv, rows, cap))
+    return list(surv[:k]), [list(rows[t * rw:(t + 1) * rw]) for t in range(w)]
+
+
+def heal_wrows(coding, params, mask, r):
+    """leoec_heal_wrows (no device needed): the map heal_ws() rebuilds the r-th
+    lost id (ascending, from 0) of ``mask`` with for a vandrs or isars code
+    outside heal()'s one-launch family.  Returns ``(surv, coef)``: the k
+    survivor ids (the first k intact ids ascending) and the k GF(2^w)
+    coefficients that give the lost block from them."""
+    k, m, w = params
+    surv = (ctypes.c_int * max(k, 1))()
+    coef = (ctypes.c_uint32 * max(k, 1))()
+    _lib.check(lib.leoec_heal_wrows(_cid(coding), k, m, w, mask, r, surv, coef, max(k, 1)))
+    return list(surv[:k]), list(coef[:k])
+
+
 def locate_bitrows(coding, params):
     """leoec_locate_bitrows (no device needed): the GF(2) ratios locate_ws()
     tests the syndromes of cauchyrs and liberation with: ``m - 1`` lists of k
