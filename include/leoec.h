@@ -133,7 +133,8 @@ int leoec_repair(int coding, int k, int m, int w, const uint8_t *const *blocks, 
  * m*block_size, block/out strides >= block_size) for every nobj >= 1;
  * otherwise LEOEC_E_ARG.  The buffers themselves cannot be checked here:
  * they must hold nobj rows.
- * leoec_encode_dev, leoec_decode_dev, leoec_repair_dev, leoec_verify_dev
+ * leoec_encode_dev, leoec_decode_dev, leoec_repair_dev, leoec_update_dev,
+ * leoec_verify_dev
  * (with and without a workspace), the three locate and the three scrub calls
  * (leoec_scrub_gfw_dev serves every class a locate call names one block for,
  * up to k + m = 31) and leoec_heal_dev where it takes one launch (see there:
@@ -307,6 +308,59 @@ int leoec_heal_ws_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t o
                       uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
                       const uint32_t *lost, uint32_t *unhealed, uint32_t *totals, void *workspace,
                       uint64_t workspace_bytes, void *stream);
+
+/* Overwrite object bytes [offset, offset + length) of every object of a
+ * stored batch with the patch, and patch the parity to match, in place.  The
+ * layout, alignment and stride rules are leoec_encode_dev's; the range is in
+ * object bytes and the same for every object (one range per object: nobj = 1).
+ * patch: device, 16-byte aligned, patch_stride a multiple of 16 and at least
+ * lead + length, lead = offset % 16.  Row o starts at the 16-byte lane that
+ * holds `offset`: the new value of object byte p is
+ * patch[o * patch_stride + lead + (p - offset)].  The first lead bytes of a
+ * row and the bytes past lead + length are never read; patch is never written.
+ * After the call, with D the object of `size` bytes that is old ^ new inside
+ * the range and zero elsewhere:
+ *   - objs bytes [offset, offset + length) hold the patch; every other byte of
+ *     the row keeps its value, bytes past `size` included;
+ *   - the parity row is the parity row before the call XOR leoec_encode_dev's
+ *     coding blocks of D, byte for byte.  A stripe that was consistent is the
+ *     encoding of the new object.  A stripe that was damaged keeps exactly its
+ *     syndrome: update never hides corruption from a later scrub, and never
+ *     repairs any;
+ *   - a parity byte the encoding of D cannot reach keeps its value: for vandrs
+ *     and isars every column outside the w-bit words the range touches (the
+ *     16-byte lanes that hold them are rewritten with the bytes they held), for
+ *     cauchyrs and liberation every packet position outside the touched ones; a
+ *     coding packet whose bit-row has no set bit among the touched data packets
+ *     of a position is neither read nor written there.
+ * The range is split at data-block boundaries: one launch per touched data
+ * block and 4 coding blocks (vandrs, isars) or 64 coding packets (cauchyrs,
+ * liberation), in stream order; (3 + 2m) bytes move per patched byte.  Nothing
+ * is allocated, uploaded or waited for, the coefficients travel as kernel
+ * arguments, so the call can be captured into a graph after the first call of
+ * a code (its host plan, this call's code object).  Serves every
+ * configuration leoec_encode_dev serves, k + m > 32 included.
+ * Statuses, in this order: leoec_check_params' for the layout and parameters;
+ * LEOEC_OK with nothing written for nobj, length or size 0; LEOEC_E_BAD_SIZE
+ * when offset + length exceeds `size` or wraps; LEOEC_E_ARG for a NULL or
+ * misaligned pointer, a stride that breaks the rules above, or a patch extent
+ * ((nobj - 1) * patch_stride + lead + length bytes) that overlaps the extent of
+ * objs or parity (LEOEC_E_BAD_SIZE: a block of 4 GiB or more); then the
+ * device.
+ * Against the path without this call (a device copy of the patch into objs,
+ * then leoec_encode_dev of the whole object), measured on an MI355X with
+ * 2,048 objects of 1 MiB (tools/update_bench.py, profiles/update_bench.txt):
+ * a 4 KiB patch takes 0.020-0.057 ms against 0.48-0.60 ms (0.03-0.11 of it), a
+ * 64 KiB patch 0.31-0.73 of it, and update stops winning at a patch of about
+ * 143 KB for vandrs(10,4,8), 158 KB for vandrs(10,4,16), 115 KB for
+ * cauchyrs(10,4,8) and 254 KB for liberation(4,2,7): near
+ * (size + m * block_size) / (1 + 2m) bytes, where the two traffic models meet.
+ * A longer patch belongs to the copy and leoec_encode_dev (the whole object:
+ * update takes 2.1-3.2 times as long). */
+int leoec_update_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t obj_stride,
+                     uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
+                     const uint8_t *patch, uint64_t patch_stride, uint64_t offset,
+                     uint64_t length, void *stream);
 
 /* leoec_locate_dev's word for an object that is inconsistent in a way no
  * single block explains.  The bit lies at or above k + m, so leoec_heal_dev

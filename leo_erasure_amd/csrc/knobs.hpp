@@ -132,6 +132,10 @@ struct Knobs {
   int heal_ws_chunk = 0;     // LEOEC_HEAL_WS_CHUNK=n: leoec_heal_ws_dev in chunks of at most n objects
                              //   (the chunk seam at test-sized batches; 0: the shipped chunk, which
                              //   only keeps a launch's item count below 2^31)
+  // update.hip
+  int update_chunk = 0;      // LEOEC_UPDATE_CHUNK=n: leoec_update_dev in chunks of at most n objects
+                             //   (the chunk seam at test-sized batches; 0: the shipped chunk, which
+                             //   only keeps a launch's grid below 2^31)
 };
 
 const Knobs& knobs();

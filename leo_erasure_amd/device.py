@@ -492,6 +492,23 @@ def heal_ws(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, 
     return unhealed, totals
 
 
+def update(coding, params, objs, size, parity, patch, offset, length, nobj=None, stream=None):
+    """leoec_update_dev: overwrite object bytes ``[offset, offset + length)`` of
+    every object of the batch with ``patch`` and patch the parity to match, in
+    place: parity ^= the coding blocks of (old ^ new), so a consistent stripe
+    stays consistent and a damaged one keeps its syndrome.  ``patch`` is
+    ``[nobj, patch_stride]``; row o starts at the 16-byte lane that holds
+    ``offset``: the new value of object byte p is
+    ``patch[o, offset % 16 + (p - offset)]``."""
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
+    if offset < 0 or length < 0:
+        raise ValueError("update: negative offset or length")
+    _rows(patch, nobj, offset % 16 + length if length else 0, "patch")
+    _lib.check(lib.leoec_update_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                    nobj, parity.data_ptr(), _row_stride(parity), patch.data_ptr(),
+                                    _row_stride(patch), offset, length, _stream(stream)))
+
+
 def heal_bitrows(coding, params, mask, r):
     """leoec_heal_bitrows (no device needed): the map heal_ws() rebuilds the
     r-th lost id (ascending, from 0) of ``mask`` of a cauchyrs or liberation
