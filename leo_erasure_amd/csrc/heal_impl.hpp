@@ -14,6 +14,11 @@
 // Launch geometry and the workgroup -> (object, tile) decode are gf8_apply's
 // (gf8_grid_env, gf8_wg_tile in kernels_impl.hpp): HealArgs carries the same
 // tiles / nobj / tmap / tperm fields as Gf8Args.
+//
+// Everything after the mask test is gf8_heal_tile, which gf8_heal_list
+// (scrub_impl.hpp) calls per item of its list.  What every list kernel and
+// its launcher take from here besides: uniform_word, heal_shard, list_append
+// (the listing step) and list_grid (the fixed grid).
 #pragma once
 
 #include "heal_table.hpp"
@@ -87,20 +92,65 @@ __device__ __forceinline__ DevShard heal_shard(const HealArgs& a, const uint8_t*
   return s;
 }
 
-template <int K, int R, int WAVES>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
-gf8_heal(const HealArgs a) {
+// The listing step's compaction, one lane per object i of the chunk.  A wave
+// whose lanes say `one` (rebuild this object) takes its stretch of the list
+// with one atomicAdd on *count (list != nullptr) and adds their number to
+// totals[0] with another; one whose lanes say `many` adds theirs to totals[1].
+// A wave with neither issues no atomic.  No lane leaves early before this:
+// lanes past the chunk come with neither, so lane 0 is there to issue the
+// wave's atomics.  The order of the list is whatever order the waves arrive in.
+// Changing this changes 2 kernels: scrub_finish (scrub.hip) and heal_ws_list
+// (heal_ws_impl.hpp).
+__device__ __forceinline__ void list_append(bool one, bool many, uint32_t i,
+                                            uint32_t* __restrict__ list,
+                                            uint32_t* __restrict__ count,
+                                            uint32_t* __restrict__ totals) {
+  const uint64_t b1 = __builtin_amdgcn_ballot_w64(one);
+  const uint64_t bm = __builtin_amdgcn_ballot_w64(many);
+  if ((b1 | bm) == 0ull) return;  // wave-uniform
+  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if (b1 != 0ull) {
+    const uint32_t c = (uint32_t)__builtin_popcountll(b1);
+    uint32_t base = 0;
+    if (lane == 0u) {
+      if (list) base = atomicAdd(count, c);
+      atomicAdd(&totals[0], c);
+    }
+    base = __builtin_amdgcn_readfirstlane(base);
+    // the lane's rank among the wave's listed lanes
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32),
+                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
+    if (list && one) list[base + rank] = i;
+  }
+  if (bm != 0ull && lane == 0u) atomicAdd(&totals[1], (uint32_t)__builtin_popcountll(bm));
+}
+
+// The fixed grid of a list kernel, whose item count the host does not know:
+// min(all items the chunk could list, resident workgroups of the device), at
+// most `cap` workgroups when cap is not 0 (LEOEC_SCRUB_GRID, measurement
+// build).  resident: workgroups of the kernel a compute unit holds at once.
+inline uint32_t list_grid(uint64_t all, uint32_t resident, uint32_t cap) {
+  uint64_t grid = (uint64_t)device_cus() * resident;
+  grid = grid < all ? grid : all;
+  if (cap != 0u && grid > cap) grid = cap;
+  return (uint32_t)grid;
+}
+
+// One (object, tile) of the fused rebuild: the record of the object's mask, its
+// tables into lds, its shards and the tile.  mask: the object's word,
+// recoverable and not 0 (workgroup-uniform); lds: the kernel's own, free to be
+// staged (a kernel that loops puts a barrier between two calls); TBr: the tile
+// width, blockDim.x * 16 (the workgroup is 256 or 64 lanes).  The kernel reads
+// it, not this function: gf8_heal does so before its mask test, where the load
+// is in flight with the mask's (read here, it waits once more on the damaged
+// path).
+// Changing this changes 32 kernels: gf8_heal<K> (leoec_heal_dev) and
+// gf8_heal_list<K> (scrub_impl.hpp: leoec_scrub_dev, leoec_heal_ws_dev), K = 1..16.
+template <int K, int R>
+__device__ __forceinline__ void gf8_heal_tile(const HealArgs& a, Gf8Lds<K, R>& lds, uint32_t TBr,
+                                              uint32_t obj, uint32_t tile, uint32_t mask) {
   constexpr uint32_t CS = (uint32_t)kThreads * 16u;
-  const uint32_t TBr = blockDim.x * 16u;  // tile width = workgroup size (256 or 64 lanes)
-  uint32_t obj, tile;
-  gf8_wg_tile<0>(a, obj, tile);
-  // 1. the object's mask: clean and unrecoverable objects leave here, the
-  //    whole workgroup at once and before any barrier
-  const uint32_t mask = __builtin_amdgcn_readfirstlane(a.lost[obj]);
   const uint32_t bits = (uint32_t)__builtin_popcount(mask);
-  const bool bad = bits > a.m || ((uint64_t)mask >> (a.k + a.m)) != 0ull;
-  if (tile == 0u && threadIdx.x == 0u) a.unhealed[obj] = bad ? mask : 0u;
-  if (mask == 0u || bad) return;
   // 2. its record: first[bits] + sum of C(b_i, i) over the set bits ascending
   //    (no branch around a table load: the loads of a conditional step wait
   //    for one another, five memory latencies in a row before the record's
@@ -121,7 +171,6 @@ gf8_heal(const HealArgs a) {
 #pragma unroll
   for (int x = 0; x < (K + R + 3) / 4; ++x) idw[x] = rec[x];
   // 3. its tables (the record holds m rows; gf8_tile multiplies R)
-  __shared__ Gf8Lds<K, R> lds;
   for (uint32_t i = threadIdx.x; i < (uint32_t)(R * K); i += blockDim.x) {
     u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
     if (i < a.m * (uint32_t)K) {
@@ -184,6 +233,24 @@ gf8_heal(const HealArgs a) {
       if (off < valid && off + 16u > valid) store_guarded(base, off, valid, acc[0][r]);
     }
   }
+}
+
+template <int K, int R, int WAVES>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
+gf8_heal(const HealArgs a) {
+  __shared__ Gf8Lds<K, R> lds;
+  const uint32_t TBr = blockDim.x * 16u;
+  uint32_t obj, tile;
+  gf8_wg_tile<0>(a, obj, tile);
+  // 1. the object's mask: clean and unrecoverable objects leave here, the
+  //    whole workgroup at once and before any barrier
+  const uint32_t mask = __builtin_amdgcn_readfirstlane(a.lost[obj]);
+  const uint32_t bits = (uint32_t)__builtin_popcount(mask);
+  const bool bad = bits > a.m || ((uint64_t)mask >> (a.k + a.m)) != 0ull;
+  if (tile == 0u && threadIdx.x == 0u) a.unhealed[obj] = bad ? mask : 0u;
+  if (mask == 0u || bad) return;
+  // 2 to 5. its record, tables, shards and tile
+  gf8_heal_tile<K, R>(a, lds, TBr, obj, tile, mask);
 }
 
 // The shipped gf8_apply form's grid (gf8_grid_env) over the objects a

@@ -24,9 +24,9 @@
 //                                   is cached per (code, device) in a cache of
 //                                   this unit's own (dev_table.hpp).
 // A chunk exists only to keep a launch's item count below 2^31.
-// Workspace: leoec_scrub_dev's, a 16-byte header, then one index word per
-// object.  A code is served when its table exists (heal_ws_shape: at most
-// 8 MiB), which is decided without a device.
+// Workspace: leoec_scrub_dev's (scrub_impl.hpp), a 16-byte header, then one
+// index word per object.  A code is served when its table exists
+// (heal_ws_shape: at most 8 MiB), which is decided without a device.
 // When the table cache is full the call is heal_ws_list counting only (the
 // totals and unhealed, no list), then op_heal_dev's own path, which
 // synchronises once.
@@ -53,14 +53,6 @@ using namespace detail;
 
 namespace {
 
-constexpr uint64_t kHealWsHeader = 16;  // bytes; word 0: the chunk's count (leoec_scrub_dev's)
-
-template <std::size_t... I>
-HealListFn gf8_heal_list_pick(std::index_sequence<I...>, int k) {
-  static HealListFn (*const sel[])() = {&gf8_heal_list_launcher<(int)I + 1>...};
-  return sel[k - 1]();
-}
-
 // leoec_heal_dev's fused family, the other word codes, the packet classes.
 enum class HealWsKind { gf8, gfw, bit };
 
@@ -79,22 +71,6 @@ int heal_ws_served(int coding, int k, int m, int w, HealWsClass* out) {
   }
   *out = bit_class(coding) ? HealWsClass{HealWsKind::bit, w} : HealWsClass{HealWsKind::gfw, 1};
   return heal_ws_shape(k, m, out->per, nullptr);
-}
-
-// Bytes of workspace for nobj objects (leoec_scrub_dev's); false when that
-// overflows.
-bool heal_ws_workspace(uint64_t nobj, uint64_t* bytes) {
-  uint64_t words;
-  if (__builtin_mul_overflow(nobj, (uint64_t)sizeof(uint32_t), &words) ||
-      __builtin_add_overflow(words, (uint64_t)15, &words))
-    return false;
-  return !__builtin_add_overflow(words & ~(uint64_t)15, kHealWsHeader, bytes);
-}
-
-// [p, p + n) meets [q, q + qn) (no sum that could wrap).
-bool overlaps(const void* p, uint64_t n, const void* q, uint64_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a >= b ? a - b < qn : b - a < n;
 }
 
 // The maps of `nwant` lost ids in a record's order (heal_ws_table.hpp).
@@ -171,7 +147,7 @@ int op_heal_ws_dev_workspace(int coding, int k, int m, int w, uint64_t size, uin
   HealWsClass cl;
   if ((rc = heal_ws_served(coding, k, m, w, &cl))) return rc;
   if (!bytes) return LEOEC_E_ARG;
-  return heal_ws_workspace(nobj, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
+  return scrub_workspace(nobj, bytes) ? LEOEC_OK : LEOEC_E_BAD_SIZE;
 }
 
 int op_heal_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_stride,
@@ -190,7 +166,7 @@ int op_heal_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_
   if ((rc = check_dev_batch(objs, obj_stride, size, parity, parity_stride, m, bs))) return rc;
   if (!workspace || ((uintptr_t)workspace & 15u)) return LEOEC_E_ARG;
   uint64_t need;
-  if (!heal_ws_workspace(nobj, &need)) return LEOEC_E_BAD_SIZE;
+  if (!scrub_workspace(nobj, &need)) return LEOEC_E_BAD_SIZE;
   if (workspace_bytes < need) return LEOEC_E_ARG;
   if (overlaps(unhealed, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
       overlaps(lost, nobj * sizeof(uint32_t), workspace, workspace_bytes) ||
@@ -203,11 +179,11 @@ int op_heal_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_
   if ((rc = cl.kind == HealWsKind::gf8 ? heal_table(*c, &table) : heal_ws_table(*c, cl.per, &table)))
     return rc;
   uint32_t* const header = static_cast<uint32_t*>(workspace);
-  uint32_t* const list = header + kHealWsHeader / sizeof(uint32_t);
+  uint32_t* const list = header + kScrubHeader / sizeof(uint32_t);
   // tiles of a block (gfw), of a packet (bit); gf8: gf8_max_objects' bound
   const uint32_t ps = cl.kind == HealWsKind::bit ? (uint32_t)(bs / (uint64_t)w) : 0u;
   const uint64_t tiles = cl.kind == HealWsKind::gfw   ? (bs + kGfwHealTile - 1) / kGfwHealTile
-                         : cl.kind == HealWsKind::bit ? (ps + kBitMasksTile - 1u) / kBitMasksTile
+                         : cl.kind == HealWsKind::bit ? (ps + kBitHealTile - 1u) / kBitHealTile
                                                       : 0;
   // objects of a launch: items = objects x m x tiles < 2^31 (bs < 2^32, m <= 31)
   uint64_t max_obj = cl.kind == HealWsKind::gf8 ? gf8_max_objects(bs)
@@ -255,7 +231,7 @@ int op_heal_ws_dev(int coding, int k, int m, int w, uint8_t* objs, uint64_t obj_
       g.red = field(8).mul(0x80u, 2u);  // alpha^8 reduced: the polynomial's low byte
       rc = launch_gfw_heal_masks(w, g, list, header, cap, s);
     } else {
-      BitMasksArgs a;
+      BitHealArgs a;
       a.h = h;
       a.w = (uint32_t)w;
       a.ps = ps;

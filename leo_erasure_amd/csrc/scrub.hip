@@ -70,23 +70,11 @@ using namespace detail;
 
 namespace {
 
-constexpr uint64_t kScrubHeader = 16;  // bytes; word 0: the chunk's count
-
-template <std::size_t... I>
-HealListFn gf8_heal_list_pick(std::index_sequence<I...>, int k) {
-  static HealListFn (*const sel[])() = {&gf8_heal_list_launcher<(int)I + 1>...};
-  return sel[k - 1]();
-}
-
 // locate_finish (locate.hip) with the compaction in it.  One word per lane, in
 // place: all ones -> 0, exactly one bit -> kept, anything else ->
-// LEOEC_LOCATE_MANY.  A wave with single-bit words takes its stretch of the
-// list with one atomicAdd on *count (list != nullptr) and adds their number to
-// totals[0] with another; one with LEOEC_LOCATE_MANY words adds theirs to
-// totals[1].  A wave with neither issues no atomic: a clean batch writes its
-// words and nothing else.  No lane leaves early: lanes past n hold a clean
-// word, so lane 0 is there to issue the wave's atomics.  The order of the list
-// is whatever order the waves arrive in.
+// LEOEC_LOCATE_MANY.  The single-bit words are listed and counted into
+// totals[0], the LEOEC_LOCATE_MANY words into totals[1] (list_append,
+// heal_impl.hpp): a clean batch writes its words and nothing else.
 __global__ void __launch_bounds__(kThreads)
 scrub_finish(uint32_t* __restrict__ words, uint32_t n, uint32_t* __restrict__ list,
              uint32_t* __restrict__ count, uint32_t* __restrict__ totals) {
@@ -100,39 +88,7 @@ scrub_finish(uint32_t* __restrict__ words, uint32_t n, uint32_t* __restrict__ li
   // which refuse k + m = 32 for this line's sake)
   const bool many = f == LEOEC_LOCATE_MANY;
   const bool one = f != 0u && !many;
-  const uint64_t b1 = __builtin_amdgcn_ballot_w64(one);
-  const uint64_t bm = __builtin_amdgcn_ballot_w64(many);
-  if ((b1 | bm) == 0ull) return;  // wave-uniform
-  const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  if (b1 != 0ull) {
-    const uint32_t c = (uint32_t)__builtin_popcountll(b1);
-    uint32_t base = 0;
-    if (lane == 0u) {
-      if (list) base = atomicAdd(count, c);
-      atomicAdd(&totals[0], c);
-    }
-    base = __builtin_amdgcn_readfirstlane(base);
-    // the lane's rank among the wave's single-bit lanes
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32),
-                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u));
-    if (list && one) list[base + rank] = i;
-  }
-  if (bm != 0ull && lane == 0u) atomicAdd(&totals[1], (uint32_t)__builtin_popcountll(bm));
-}
-
-// Bytes of workspace for nobj objects; false when that overflows.
-bool scrub_workspace(uint64_t nobj, uint64_t* bytes) {
-  uint64_t words;
-  if (__builtin_mul_overflow(nobj, (uint64_t)sizeof(uint32_t), &words) ||
-      __builtin_add_overflow(words, (uint64_t)15, &words))
-    return false;
-  return !__builtin_add_overflow(words & ~(uint64_t)15, kScrubHeader, bytes);
-}
-
-// [p, p + n) meets [q, q + qn) (no sum that could wrap).
-bool overlaps(const void* p, uint64_t n, const void* q, uint64_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a >= b ? a - b < qn : b - a < n;
+  list_append(one, many, i, list, count, totals);
 }
 
 int op_scrub_dev_workspace(int coding, int k, int m, int w, uint64_t size, uint64_t nobj,

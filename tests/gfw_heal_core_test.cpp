@@ -1,5 +1,5 @@
 // TEST PROGRAM (CPU) for the portable core of leo_erasure_amd/csrc/
-// scrub_gfw_impl.hpp: gfwheal::mac_in<W> and gfwheal::from_domain<W>, the
+// gfw_heal_tile.hpp: gfwheal::mac_in<W> and gfwheal::from_domain<W>, the
 // per-lane arithmetic "acc ^= c * x" and the way back to bytes that
 // gfw_heal_list runs on the GPU, against field arithmetic taken from the
 // oracle.  Stand-alone (its own main), so it can also be built with
@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../leo_erasure_amd/csrc/codes.hpp"
-#include "../leo_erasure_amd/csrc/scrub_gfw_impl.hpp"
+#include "../leo_erasure_amd/csrc/gfw_heal_tile.hpp"
 
 namespace {
 

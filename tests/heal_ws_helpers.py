@@ -11,7 +11,7 @@ import heal_helpers as HH
 
 TOTALS_PREFILL = 0x70771E55
 WS_FILL, WS_TAIL = 0xE7, 64
-TILE_GFW, TILE_BIT = 4096, 1024  # bytes of a block / of a packet per item (heal_ws_impl.hpp)
+TILE_GFW, TILE_BIT = 4096, 1024  # bytes of a block / of a packet per item (gfw_heal_tile.hpp, bit_heal_tile.hpp)
 
 # the configurations the call must serve beside heal_helpers.FAMILIES, and one
 # it must refuse
@@ -179,6 +179,6 @@ def mask_case(le, oracle, cfg, B, masks):
 
 
 def resident(cls, w):
-    """Workgroups of the rebuild kernel a compute unit holds (heal_ws_impl.hpp,
-    restated): gfw_heal_masks 16, bit_heal_masks min(32, 160 // w)."""
+    """Workgroups of the rebuild kernel a compute unit holds (gfw_heal_tile.hpp,
+    bit_heal_tile.hpp, restated): gfw_heal_masks 16, bit_heal_masks min(32, 160 // w)."""
     return min(32, 160 // w) if cls in ("cauchyrs", "liberation") else 16

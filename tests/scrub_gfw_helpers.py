@@ -15,7 +15,7 @@ import scrub_helpers as S
 MANY = L.MANY
 WS_FILL, WS_TAIL, TOTALS_PREFILL = D.WS_FILL, D.WS_TAIL, D.TOTALS_PREFILL
 _hex, _u32 = D._hex, D._u32
-TILE = 4096  # bytes of a block one workgroup of gfw_heal_list takes per item (scrub_gfw_impl.hpp)
+TILE = 4096  # bytes of a block one workgroup of gfw_heal_list takes per item (gfw_heal_tile.hpp)
 FAMILIES = G.FAMILIES
 LAST = ("vandrs", 16, 15, 8, 8704)  # k + m = 31: the last id the report has a bit for
 
@@ -204,12 +204,12 @@ def check_whole(gpu, le, case, blocks, room=None, composed=True):
 
 
 def gfw_heal_list_resident():
-    """gfw_heal_list_resident() of scrub_gfw_impl.hpp, restated: one wave per
+    """gfw_heal_list_resident() of gfw_heal_tile.hpp, restated: one wave per
     workgroup, 4 waves on each of a compute unit's 4 SIMDs."""
     return 16
 
 
 def grid(cus, nobj, tiles, cap=0):
-    """launch_gfw_heal_list's grid, restated."""
+    """launch_gfw_heal_list's grid (list_grid, heal_impl.hpp), restated."""
     g = min(cus * gfw_heal_list_resident(), nobj * tiles)
     return min(g, cap) if cap else g

@@ -12,7 +12,7 @@ import scrub_helpers as S
 MANY = L.MANY
 WS_FILL, WS_TAIL, TOTALS_PREFILL = D.WS_FILL, D.WS_TAIL, D.TOTALS_PREFILL
 _hex, _u32 = D._hex, D._u32
-TILE = 1024  # bytes of a packet one workgroup of bit_heal_list takes (scrub_bit_impl.hpp)
+TILE = 1024  # bytes of a packet one workgroup of bit_heal_list takes (bit_heal_tile.hpp)
 
 
 def cases(le, oracle, family):

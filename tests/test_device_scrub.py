@@ -143,8 +143,14 @@ def test_grid_constants_are_the_sources():
     assert "constexpr int kGf8HealWaves = LEOEC_GF8_HEAL_WAVES;" in heal
     assert ("inline uint32_t gf8_heal_list_resident(uint32_t wg) "
             "{ return 4u * (uint32_t)kGf8HealWaves * 64u / wg; }") in scrub
-    assert "uint64_t grid = (uint64_t)device_cus() * gf8_heal_list_resident(wg);" in scrub
-    assert "grid = grid < all ? grid : all;" in scrub
+    # the grid rule: list_grid, the one function every list kernel's launcher calls
+    assert ("const uint32_t grid = list_grid((uint64_t)a.nobj * a.tiles, gf8_heal_list_resident(wg), cap);"
+            in scrub)
+    assert re.search(r"inline uint32_t list_grid\(uint64_t all, uint32_t resident, uint32_t cap\) \{\s*"
+                     r"uint64_t grid = \(uint64_t\)device_cus\(\) \* resident;\s*"
+                     r"grid = grid < all \? grid : all;\s*"
+                     r"if \(cap != 0u && grid > cap\) grid = cap;\s*"
+                     r"return \(uint32_t\)grid;\s*\}", heal)
     assert gf8_heal_list_resident(256) == 4 and gf8_heal_list_resident(64) == 16
     cls, k, m, w, B = LARGE
     assert B <= 160 * 1024 and -(-B // 4096) == 2  # the 256-lane form, two tiles a block

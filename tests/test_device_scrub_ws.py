@@ -163,7 +163,7 @@ def test_device_scrub_ws_whole_blocks(gpu, le, oracle, family):
 
 
 # bit_heal_list's grid, restated: compute units x resident workgroups
-# (scrub_bit_impl.hpp: one wave each, 32 waves a compute unit, w KiB of its
+# (bit_heal_tile.hpp: one wave each, 32 waves a compute unit, w KiB of its
 # 160 KiB of LDS each)
 # (m = 3: neither side builds an m = 2 Cauchy matrix past w = 20)
 LARGE = ("cauchyrs", 2, 3, 32, 1040 * 32)  # packets of 1,040 bytes: a full tile and a 16-byte one
@@ -175,15 +175,22 @@ def bit_heal_list_resident(w):
 
 def test_grid_constants_are_the_sources(le, oracle):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "leo_erasure_amd", "csrc", "scrub_bit_impl.hpp")) as fh:
+    csrc = os.path.join(root, "leo_erasure_amd", "csrc")
+    with open(os.path.join(csrc, "bit_heal_tile.hpp")) as fh:  # the constants and resident()
         text = fh.read()
+    with open(os.path.join(csrc, "scrub_bit_impl.hpp")) as fh:  # the launcher
+        launch = fh.read()
+    with open(os.path.join(csrc, "heal_impl.hpp")) as fh:  # list_grid
+        heal = fh.read()
     assert re.findall(r"constexpr int kBitHealLanes = (\d+);", text) == ["64"]
     assert "constexpr uint32_t kBitHealTile = kBitHealLanes * 16u;" in text and X.TILE == 64 * 16
     assert re.search(r"inline uint32_t bit_heal_list_resident\(uint32_t w\) \{\s*"
                      r"const uint32_t by_lds = 160u / w;[^\n]*\n\s*"
                      r"return by_lds < 32u \? by_lds : 32u;\s*\}", text)
-    assert "uint64_t grid = (uint64_t)device_cus() * bit_heal_list_resident(a.w);" in text
-    assert "grid = grid < all ? grid : all;" in text
+    assert ("const uint32_t grid = list_grid((uint64_t)a.h.nobj * a.h.tiles, bit_heal_list_resident(a.w), cap);"
+            in launch)
+    assert "uint64_t grid = (uint64_t)device_cus() * resident;" in heal
+    assert "grid = grid < all ? grid : all;" in heal
     assert [bit_heal_list_resident(w) for w in (2, 5, 6, 17, 32)] == [32, 32, 26, 9, 5]
     cls, k, m, w, B = LARGE
     assert B % (16 * w) == 0 and -(-(B // w) // X.TILE) == 2 and W.served(cls, k, m, w)

@@ -19,7 +19,7 @@ OBJS = {"product": os.path.join(CSRC, "_build", "heal_ws.o"),
         "measure": os.path.join(CSRC, "_build_measure", "heal_ws.o")}
 GFW = "_ZN5leoec6detail14gfw_heal_masksILi%dEEEvNS0_11GfwHealArgsEPKjS4_"
 WANT = sorted([GFW % w for w in (8, 16, 32)] +
-              ["_ZN5leoec6detail14bit_heal_masksENS0_12BitMasksArgsEPKjS3_",
+              ["_ZN5leoec6detail14bit_heal_masksENS0_11BitHealArgsEPKjS3_",
                "_ZN5leoec6detail12heal_ws_listEPKjPjjjjS3_S3_S3_",
                "_ZN5leoec6detail13heal_ws_beginEPjS1_"])
 

@@ -9,7 +9,7 @@ register or use scratch (a spilling kernel's first launch makes the runtime
 back the whole device's scratch, test_code_objects.py), and each must fit the
 4-wave register budget its fixed grid counts on (gfw_heal_list_resident: 16
 workgroups a compute unit).  No LDS; one wave per workgroup; the table is in
-memory, so the argument segment is what scrub_gfw_impl.hpp asserts.  Metadata
+memory, so the argument segment is what gfw_heal_tile.hpp asserts.  Metadata
 only, read as test_locate_ws_code_object.py reads it."""
 import os
 import re
@@ -22,7 +22,7 @@ import test_locate_ws_code_object as CO
 CSRC = os.path.join(CO.ROOT, "leo_erasure_amd", "csrc")
 OBJS = {"product": os.path.join(CSRC, "_build", "scrub.o"),
         "measure": os.path.join(CSRC, "_build_measure", "scrub.o")}
-SRC = os.path.join(CSRC, "scrub_gfw_impl.hpp")
+SRC = os.path.join(CSRC, "gfw_heal_tile.hpp")  # the constants, GfwHealArgs and resident()
 NAME = "_ZN5leoec6detail13gfw_heal_listILi%dEEEvNS0_11GfwHealArgsEPKjS4_"
 
 
@@ -34,7 +34,7 @@ def _source():
 def asserted_argument_bytes():
     """The explicit argument bytes the source's static_assert states."""
     m = re.search(r"static_assert\(sizeof\(GfwHealArgs\) \+ 2 \* sizeof\(uint32_t\*\) == (\d+),", _source())
-    assert m, "scrub_gfw_impl.hpp: the argument segment's static_assert"
+    assert m, "gfw_heal_tile.hpp: the argument segment's static_assert"
     return int(m.group(1))
 
 
@@ -54,9 +54,15 @@ def test_geometry_constants_are_the_sources():
     assert re.findall(r"constexpr int kGfwHealWaves = (\d+);", text) == ["4"]
     assert "inline uint32_t gfw_heal_list_resident() { return 4u * (uint32_t)kGfwHealWaves; }" in text
     assert X.gfw_heal_list_resident() == 4 * 4
-    assert "uint64_t grid = (uint64_t)device_cus() * gfw_heal_list_resident();" in text
-    assert "grid = grid < all ? grid : all;" in text
-    assert "if (cap != 0u && grid > cap) grid = cap;" in text
+    # the grid rule: the launcher hands its items and resident() to list_grid
+    with open(os.path.join(CSRC, "scrub_gfw_impl.hpp")) as f:
+        assert ("const dim3 g(list_grid((uint64_t)a.h.nobj * a.h.tiles, gfw_heal_list_resident(), cap));"
+                in f.read())
+    with open(os.path.join(CSRC, "heal_impl.hpp")) as f:
+        heal = f.read()
+    assert "uint64_t grid = (uint64_t)device_cus() * resident;" in heal
+    assert "grid = grid < all ? grid : all;" in heal
+    assert "if (cap != 0u && grid > cap) grid = cap;" in heal
     assert X.grid(256, 10, 3) == 30 and X.grid(256, 2048, 3) == 4096 and X.grid(256, 2048, 3, 7) == 7
 
 

@@ -12,7 +12,7 @@ serves is forwarded to it.
 
 leoec_scrub_wrows is a record of the table the device gets: it is held against
 leoec_heal_rows and against the oracle's blocks.  The per-lane arithmetic of
-gfw_heal_list (scrub_gfw_impl.hpp's portable core) is compiled for the CPU and
+gfw_heal_list (gfw_heal_tile.hpp's portable core) is compiled for the CPU and
 run against the oracle's field as a stand-alone program, once more under
 ASan + UBSan.  The by-construction words test_device_scrub_gfw.py expects of
 the device are held against locate_gfw_helpers' host model."""

@@ -45,7 +45,7 @@ GRIDS = ("1", str(CAP), None)
 def kernel_tile():
     """The tile width bit_heal_list really has: kBitHealLanes x 16 bytes."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "leo_erasure_amd", "csrc", "scrub_bit_impl.hpp")) as f:
+    with open(os.path.join(root, "leo_erasure_amd", "csrc", "bit_heal_tile.hpp")) as f:
         text = f.read()
     lanes = int(re.search(r"constexpr int kBitHealLanes = (\d+);", text).group(1))
     assert re.search(r"constexpr uint32_t kBitHealTile = kBitHealLanes \* 16u;", text)
