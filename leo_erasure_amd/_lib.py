@@ -90,45 +90,51 @@ def _load(path=LIB_PATH):
                                              u64, u8p]
     L.leoec_repair.argtypes = [c_int] * 4 + [ctypes.POINTER(vp), ctypes.POINTER(c_int), c_int, u64,
                                              ctypes.POINTER(c_int), c_int, u8p]
-    L.leoec_encode_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp]
-    L.leoec_decode_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64,
-                                                 ctypes.POINTER(c_int), c_int, vp]
+    # the *_dev calls: the code and the batch (objs, obj_stride, size, nobj, parity, parity_stride),
+    # the call's own arguments, the stream
+    batch = [c_int] * 4 + [vp, u64, u64, u64, vp, u64]
+    query = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]  # *_dev_workspace
+    words_cap = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]  # locate_*rows
+    words_ws = batch + [vp, vp, u64, vp]  # one words tensor, the workspace and its bytes
+    scrub = batch + [vp, vp, vp, u64, vp]  # report, totals, the workspace and its bytes
+    L.leoec_encode_dev.argtypes = batch + [vp]
+    L.leoec_decode_dev.argtypes = batch + [ctypes.POINTER(c_int), c_int, vp]
     L.leoec_repair_dev.argtypes = [c_int] * 4 + [ctypes.POINTER(vp), u64, u64, u64,
                                                  ctypes.POINTER(c_int), c_int, ctypes.POINTER(vp),
                                                  u64, vp]
     L.leoec_coding_matrix.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int,
                                                     ctypes.POINTER(c_int)]
-    L.leoec_verify_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_verify_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
-    L.leoec_heal_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp]
+    L.leoec_verify_dev_workspace.argtypes = query
+    L.leoec_verify_dev.argtypes = words_ws
+    L.leoec_heal_dev.argtypes = batch + [vp, vp, vp]
     L.leoec_heal_rows.argtypes = [c_int] * 4 + [ctypes.c_uint32, ctypes.POINTER(c_int),
                                                 ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                                                 ctypes.POINTER(ctypes.c_uint32), c_int,
                                                 ctypes.POINTER(c_int)]
-    L.leoec_locate_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp]
-    L.leoec_locate_rows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
-    L.leoec_locate_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_locate_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
-    L.leoec_locate_bitrows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
-    L.leoec_locate_gfw_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_locate_gfw_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, u64, vp]
-    L.leoec_locate_wrows.argtypes = [c_int] * 4 + [ctypes.POINTER(ctypes.c_uint32), c_int]
-    L.leoec_scrub_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_scrub_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
-    L.leoec_scrub_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_scrub_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.leoec_locate_dev.argtypes = batch + [vp, vp]
+    L.leoec_locate_rows.argtypes = words_cap
+    L.leoec_locate_ws_dev_workspace.argtypes = query
+    L.leoec_locate_ws_dev.argtypes = words_ws
+    L.leoec_locate_bitrows.argtypes = words_cap
+    L.leoec_locate_gfw_dev_workspace.argtypes = query
+    L.leoec_locate_gfw_dev.argtypes = words_ws
+    L.leoec_locate_wrows.argtypes = words_cap
+    L.leoec_scrub_dev_workspace.argtypes = query
+    L.leoec_scrub_dev.argtypes = scrub
+    L.leoec_scrub_ws_dev_workspace.argtypes = query
+    L.leoec_scrub_ws_dev.argtypes = scrub
     L.leoec_scrub_bitrows.argtypes = [c_int] * 5 + [ctypes.POINTER(c_int),
                                                     ctypes.POINTER(ctypes.c_uint32), c_int]
-    L.leoec_scrub_gfw_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_scrub_gfw_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.leoec_scrub_gfw_dev_workspace.argtypes = query
+    L.leoec_scrub_gfw_dev.argtypes = scrub
     L.leoec_scrub_wrows.argtypes = [c_int] * 5 + [ctypes.POINTER(c_int),
                                                   ctypes.POINTER(ctypes.c_uint32), c_int]
-    L.leoec_heal_ws_dev_workspace.argtypes = [c_int] * 4 + [u64, u64, ctypes.POINTER(u64)]
-    L.leoec_heal_ws_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.leoec_heal_ws_dev_workspace.argtypes = query
+    L.leoec_heal_ws_dev.argtypes = batch + [vp, vp, vp, vp, u64, vp]
     L.leoec_heal_bitrows.argtypes = [c_int] * 4 + [ctypes.c_uint32, c_int, ctypes.POINTER(c_int),
                                                    ctypes.POINTER(ctypes.c_uint32), c_int]
     L.leoec_heal_wrows.argtypes = L.leoec_heal_bitrows.argtypes
-    L.leoec_update_dev.argtypes = [c_int] * 4 + [vp, u64, u64, u64, vp, u64, vp, u64, u64, u64, vp]
+    L.leoec_update_dev.argtypes = batch + [vp, u64, u64, u64, vp]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

@@ -57,6 +57,73 @@ def _words(t, nobj, what):
         raise ValueError(f"{what}: {t.numel()} words, {nobj} needed")
 
 
+def _int32(device, optional, required=()):
+    """The int32 word tensors of a call, ``(tensor, words, name)`` each: the
+    ``optional`` ones that are None allocated on ``device``, then the
+    ``required`` and the ``optional`` ones checked in that order.  Returns the
+    optional ones."""
+    out = [torch.empty(n, dtype=torch.int32, device=device) if t is None else t
+           for t, n, _ in optional]
+    for t, n, what in required:
+        _words(t, n, what)
+    for t, (_, n, what) in zip(out, optional):
+        _words(t, n, what)
+    return out
+
+
+def _workspace_args(workspace):
+    """(pointer, bytes) of a workspace tensor, (None, 0) of none."""
+    if workspace is None:
+        return None, 0
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    return workspace.data_ptr(), workspace.numel()
+
+
+def _query(name, coding, params, size, nobj):
+    """leoec_<name>_dev_workspace: the bytes the call wants or needs."""
+    k, m, w = params
+    out = ctypes.c_uint64(0)
+    _lib.check(getattr(lib, f"leoec_{name}_dev_workspace")(_cid(coding), k, m, w, size, nobj,
+                                                           ctypes.byref(out)))
+    return out.value
+
+
+def _scrub_head(nobj):
+    """The 16-byte header and one index word per object of a scrub workspace."""
+    return 16 + (4 * nobj + 15) // 16 * 16
+
+
+def _encode_workspace(name, workspace, need, floor, device, stream, head=None):
+    """The workspace of a call that encodes into it, when the caller gave none
+    and the query said ``need``: the encode region capped at
+    ``VERIFY_WORKSPACE_CAP`` (the batch then goes in chunks) and at least
+    ``floor`` bytes, one object's, behind ``head`` bytes where the call has a
+    header.  Without a header a query of 0 needs none.  The caching allocator
+    orders a buffer's reuse only on the stream it knows about, so a call on an
+    explicit ``stream`` is not given one."""
+    if workspace is not None or (head is None and not need):
+        return workspace
+    if stream is not None:
+        least = f", at least {floor} B" if head is None else ""
+        raise ValueError(f"{name} on an explicit stream needs an explicit workspace "
+                         f"({need} B for one pass{least})")
+    enc = need - (head or 0)  # 0 for everything scrub() serves
+    if enc:
+        enc = max(min(enc, VERIFY_WORKSPACE_CAP), floor)
+    return torch.empty((head or 0) + enc, dtype=torch.uint8, device=device)
+
+
+def _fixed_workspace(name, workspace, need, device, stream):
+    """The workspace of a call that needs exactly the query's bytes, when the
+    caller gave none (and no explicit ``stream``: _encode_workspace)."""
+    if workspace is None:
+        if stream is not None:
+            raise ValueError(f"{name} on an explicit stream needs an explicit workspace ({need} B)")
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
 def _batch(coding, params, objs, size, parity, nobj):
     """(k, m, w, nobj, block size) of a batch whose tensors hold its rows."""
     k, m, w = params
@@ -90,10 +157,22 @@ VERIFY_WORKSPACE_CAP = 256 << 20  # bytes verify() allocates at most (the batch 
 def verify_workspace(coding, params, size, nobj):
     """leoec_verify_dev_workspace: bytes of workspace verify() wants for one
     pass over the batch; 0 where the check is fused into one kernel."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_verify_dev_workspace(_cid(coding), k, m, w, size, nobj, ctypes.byref(out)))
-    return out.value
+    return _query("verify", coding, params, size, nobj)
+
+
+def _pass_with_workspace(name, what, coding, params, objs, size, parity, nobj, words, workspace,
+                         stream):
+    """verify(), locate_ws() and locate_gfw(): one int32 word per object (the
+    tensor named ``what``) from a pass that encodes into a workspace."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    words, = _int32(objs.device, [(words, nobj, what)])
+    need = _query(name, coding, params, size, nobj)
+    workspace = _encode_workspace(name, workspace, need, m * bs, objs.device, stream)
+    ws_ptr, ws_bytes = _workspace_args(workspace)
+    _lib.check(getattr(lib, f"leoec_{name}_dev")(
+        _cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size, nobj, parity.data_ptr(),
+        _row_stride(parity), words.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
+    return words
 
 
 def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=None, stream=None):
@@ -103,26 +182,8 @@ def verify(coding, params, objs, size, parity, nobj=None, flags=None, workspace=
     ``workspace`` (uint8) are allocated when not given; a call on an explicit
     ``stream`` that needs a workspace must be given one, because the caching
     allocator orders a buffer's reuse only on the stream it knows about."""
-    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
-    if flags is None:
-        flags = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    _words(flags, nobj, "flags")
-    need = verify_workspace(coding, params, size, nobj)
-    if need and workspace is None:
-        if stream is not None:
-            raise ValueError("verify on an explicit stream needs an explicit workspace "
-                             f"({need} B for one pass, at least {m * bs} B)")
-        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
-                                device=objs.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-            raise ValueError("workspace: contiguous uint8 device tensor expected")
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
-    _lib.check(lib.leoec_verify_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
-                                    nobj, parity.data_ptr(), _row_stride(parity), flags.data_ptr(),
-                                    ws_ptr, ws_bytes, _stream(stream)))
-    return flags
+    return _pass_with_workspace("verify", "flags", coding, params, objs, size, parity, nobj, flags,
+                                workspace, stream)
 
 
 def heal(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, stream=None):
@@ -134,10 +195,7 @@ def heal(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, str
     cannot be recovered (more than m bits, or a bit at or above k + m), of
     which nothing is written."""
     k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
-    if unhealed is None:
-        unhealed = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    _words(lost, nobj, "lost")
-    _words(unhealed, nobj, "unhealed")
+    unhealed, = _int32(objs.device, [(unhealed, nobj, "unhealed")], [(lost, nobj, "lost")])
     _lib.check(lib.leoec_heal_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
                                   nobj, parity.data_ptr(), _row_stride(parity), lost.data_ptr(),
                                   unhealed.data_ptr(), _stream(stream)))
@@ -173,34 +231,33 @@ def locate(coding, params, objs, size, parity, nobj=None, lost=None, stream=None
     ``lost`` (int32, ``nobj`` words, allocated when not given), which heal()
     takes as it is.  vandrs w = 8 and isars with k <= 16, 2 <= m <= 4."""
     k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
-    if lost is None:
-        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    _words(lost, nobj, "lost")
+    lost, = _int32(objs.device, [(lost, nobj, "lost")])
     _lib.check(lib.leoec_locate_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
                                     nobj, parity.data_ptr(), _row_stride(parity), lost.data_ptr(),
                                     _stream(stream)))
     return lost
 
 
+def _ratio_rows(entry, coding, params):
+    """locate_rows() and locate_wrows(): ``m - 1`` lists of k ratios."""
+    k, m, w = params
+    cap = max((m - 1) * k, 1)
+    ratio = (ctypes.c_uint32 * cap)()
+    _lib.check(getattr(lib, entry)(_cid(coding), k, m, w, ratio, cap))
+    return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
+
+
 def locate_rows(coding, params):
     """leoec_locate_rows (no device needed): the ratios locate() tests the
     syndromes with, ``m - 1`` lists of k GF(2^8) coefficients, list i - 1
     holding C[i][j] / C[0][j] of the coding matrix C."""
-    k, m, w = params
-    cap = max((m - 1) * k, 1)
-    ratio = (ctypes.c_uint32 * cap)()
-    _lib.check(lib.leoec_locate_rows(_cid(coding), k, m, w, ratio, cap))
-    return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
+    return _ratio_rows("leoec_locate_rows", coding, params)
 
 
 def locate_ws_workspace(coding, params, size, nobj):
     """leoec_locate_ws_dev_workspace: bytes of workspace locate_ws() wants for
     one pass over the batch; 0 for everything locate() serves."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_locate_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
-                                                 ctypes.byref(out)))
-    return out.value
+    return _query("locate_ws", coding, params, size, nobj)
 
 
 def locate_ws(coding, params, objs, size, parity, nobj=None, lost=None, workspace=None,
@@ -210,37 +267,15 @@ def locate_ws(coding, params, objs, size, parity, nobj=None, lost=None, workspac
     ``workspace`` (uint8) follows verify()'s rules: allocated, up to
     ``VERIFY_WORKSPACE_CAP``, when not given, and required on an explicit
     ``stream``.  Returns ``lost``, which heal() takes as it is."""
-    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
-    if lost is None:
-        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    _words(lost, nobj, "lost")
-    need = locate_ws_workspace(coding, params, size, nobj)
-    if need and workspace is None:
-        if stream is not None:
-            raise ValueError("locate_ws on an explicit stream needs an explicit workspace "
-                             f"({need} B for one pass, at least {m * bs} B)")
-        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
-                                device=objs.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-            raise ValueError("workspace: contiguous uint8 device tensor expected")
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
-    _lib.check(lib.leoec_locate_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
-                                       size, nobj, parity.data_ptr(), _row_stride(parity),
-                                       lost.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
-    return lost
+    return _pass_with_workspace("locate_ws", "lost", coding, params, objs, size, parity, nobj, lost,
+                                workspace, stream)
 
 
 def locate_gfw_workspace(coding, params, size, nobj):
     """leoec_locate_gfw_dev_workspace: bytes of workspace locate_gfw() wants
     for one pass over the batch; locate_ws_workspace()'s value for everything
     locate_ws() serves."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_locate_gfw_dev_workspace(_cid(coding), k, m, w, size, nobj,
-                                                  ctypes.byref(out)))
-    return out.value
+    return _query("locate_gfw", coding, params, size, nobj)
 
 
 def locate_gfw(coding, params, objs, size, parity, nobj=None, lost=None, workspace=None,
@@ -251,26 +286,8 @@ def locate_gfw(coding, params, objs, size, parity, nobj=None, lost=None, workspa
     follows verify()'s rules: allocated, up to ``VERIFY_WORKSPACE_CAP``, when
     not given, and required on an explicit ``stream``.  Returns ``lost``,
     which heal() takes as it is."""
-    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
-    if lost is None:
-        lost = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    _words(lost, nobj, "lost")
-    need = locate_gfw_workspace(coding, params, size, nobj)
-    if need and workspace is None:
-        if stream is not None:
-            raise ValueError("locate_gfw on an explicit stream needs an explicit workspace "
-                             f"({need} B for one pass, at least {m * bs} B)")
-        workspace = torch.empty(max(min(need, VERIFY_WORKSPACE_CAP), m * bs), dtype=torch.uint8,
-                                device=objs.device)
-    ws_ptr, ws_bytes = None, 0
-    if workspace is not None:
-        if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-            raise ValueError("workspace: contiguous uint8 device tensor expected")
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel()
-    _lib.check(lib.leoec_locate_gfw_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
-                                        size, nobj, parity.data_ptr(), _row_stride(parity),
-                                        lost.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
-    return lost
+    return _pass_with_workspace("locate_gfw", "lost", coding, params, objs, size, parity, nobj, lost,
+                                workspace, stream)
 
 
 def locate_wrows(coding, params):
@@ -278,20 +295,31 @@ def locate_wrows(coding, params):
     the syndromes of the word classes with, ``m - 1`` lists of k GF(2^w)
     coefficients, list i - 1 holding C[i][j] / C[0][j] of the coding matrix
     C."""
-    k, m, w = params
-    cap = max((m - 1) * k, 1)
-    ratio = (ctypes.c_uint32 * cap)()
-    _lib.check(lib.leoec_locate_wrows(_cid(coding), k, m, w, ratio, cap))
-    return [list(ratio[i * k:(i + 1) * k]) for i in range(m - 1)]
+    return _ratio_rows("leoec_locate_wrows", coding, params)
 
 
 def scrub_workspace(coding, params, size, nobj):
     """leoec_scrub_dev_workspace: bytes of workspace scrub() needs for ``nobj``
     objects (a 16-byte header and one index word per object)."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_scrub_dev_workspace(_cid(coding), k, m, w, size, nobj, ctypes.byref(out)))
-    return out.value
+    return _query("scrub", coding, params, size, nobj)
+
+
+def _scrub(name, coding, params, objs, size, parity, nobj, report, totals, workspace, stream):
+    """scrub(), scrub_ws() and scrub_gfw(): scrub()'s workspace is the query's
+    bytes, the other two calls' the header and a capped encode region."""
+    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
+    report, totals = _int32(objs.device, [(report, nobj, "report"), (totals, 2, "totals")])
+    need = _query(name, coding, params, size, nobj)
+    if name == "scrub":
+        workspace = _fixed_workspace(name, workspace, need, objs.device, stream)
+    else:
+        workspace = _encode_workspace(name, workspace, need, m * bs, objs.device, stream,
+                                      head=_scrub_head(nobj))
+    ws_ptr, ws_bytes = _workspace_args(workspace)
+    _lib.check(getattr(lib, f"leoec_{name}_dev")(
+        _cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size, nobj, parity.data_ptr(),
+        _row_stride(parity), report.data_ptr(), totals.data_ptr(), ws_ptr, ws_bytes, _stream(stream)))
+    return report, totals
 
 
 def scrub(coding, params, objs, size, parity, nobj=None, report=None, totals=None, workspace=None,
@@ -306,25 +334,8 @@ def scrub(coding, params, objs, size, parity, nobj=None, report=None, totals=Non
     ``scrub_workspace()`` bytes) are allocated when not given; a call on an
     explicit ``stream`` must be given the workspace, for verify()'s reason.
     vandrs w = 8 and isars with k <= 16, 2 <= m <= 4."""
-    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
-    if report is None:
-        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    if totals is None:
-        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
-    _words(report, nobj, "report")
-    _words(totals, 2, "totals")
-    need = scrub_workspace(coding, params, size, nobj)
-    if workspace is None:
-        if stream is not None:
-            raise ValueError(f"scrub on an explicit stream needs an explicit workspace ({need} B)")
-        workspace = torch.empty(need, dtype=torch.uint8, device=objs.device)
-    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("workspace: contiguous uint8 device tensor expected")
-    _lib.check(lib.leoec_scrub_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
-                                   nobj, parity.data_ptr(), _row_stride(parity), report.data_ptr(),
-                                   totals.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                   _stream(stream)))
-    return report, totals
+    return _scrub("scrub", coding, params, objs, size, parity, nobj, report, totals, workspace,
+                  stream)
 
 
 def scrub_ws_workspace(coding, params, size, nobj):
@@ -332,11 +343,7 @@ def scrub_ws_workspace(coding, params, size, nobj):
     pass over the batch: scrub_workspace()'s for everything scrub() serves; for
     cauchyrs and liberation the header, one index word per object and the
     encode region of ``nobj`` objects."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_scrub_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
-                                                ctypes.byref(out)))
-    return out.value
+    return _query("scrub_ws", coding, params, size, nobj)
 
 
 def scrub_ws(coding, params, objs, size, parity, nobj=None, report=None, totals=None,
@@ -348,30 +355,30 @@ def scrub_ws(coding, params, objs, size, parity, nobj=None, report=None, totals=
     ``VERIFY_WORKSPACE_CAP`` (a smaller workspace than ``scrub_ws_workspace()``
     gives the same results in more chunks of objects), and required on an
     explicit ``stream``."""
-    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
-    if report is None:
-        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    if totals is None:
-        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
-    _words(report, nobj, "report")
-    _words(totals, 2, "totals")
-    need = scrub_ws_workspace(coding, params, size, nobj)
-    if workspace is None:
-        head = 16 + (4 * nobj + 15) // 16 * 16
-        if stream is not None:
-            raise ValueError("scrub_ws on an explicit stream needs an explicit workspace "
-                             f"({need} B for one pass)")
-        enc = need - head  # 0 for everything scrub() serves
-        if enc:
-            enc = max(min(enc, VERIFY_WORKSPACE_CAP), m * bs)
-        workspace = torch.empty(head + enc, dtype=torch.uint8, device=objs.device)
-    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("workspace: contiguous uint8 device tensor expected")
-    _lib.check(lib.leoec_scrub_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
-                                      size, nobj, parity.data_ptr(), _row_stride(parity),
-                                      report.data_ptr(), totals.data_ptr(), workspace.data_ptr(),
-                                      workspace.numel(), _stream(stream)))
-    return report, totals
+    return _scrub("scrub_ws", coding, params, objs, size, parity, nobj, report, totals, workspace,
+                  stream)
+
+
+def _bit_rows(entry, coding, params, *which):
+    """scrub_bitrows() and heal_bitrows(): the survivors and the w row lists
+    of the block ``which`` names."""
+    k, m, w = params
+    rw = (k * w + 31) // 32
+    cap = max(w * rw, 1)
+    surv = (ctypes.c_int * max(k, 1))()
+    rows = (ctypes.c_uint32 * cap)()
+    _lib.check(getattr(lib, entry)(_cid(coding), k, m, w, *which, surv, rows, cap))
+    return list(surv[:k]), [list(rows[r * rw:(r + 1) * rw]) for r in range(w)]
+
+
+def _word_rows(entry, coding, params, *which):
+    """scrub_wrows() and heal_wrows(): the survivors and the k coefficients of
+    the block ``which`` names."""
+    k, m, w = params
+    surv = (ctypes.c_int * max(k, 1))()
+    coef = (ctypes.c_uint32 * max(k, 1))()
+    _lib.check(getattr(lib, entry)(_cid(coding), k, m, w, *which, surv, coef, max(k, 1)))
+    return list(surv[:k]), list(coef[:k])
 
 
 def scrub_bitrows(coding, params, block):
@@ -380,13 +387,7 @@ def scrub_bitrows(coding, params, block):
     the k survivor ids (the first k ids ascending without ``block``) and w
     lists of ``ceil(k w / 32)`` words, bit ``i w + c`` of row r set iff packet c
     of block ``surv[i]`` feeds packet r of ``block``."""
-    k, m, w = params
-    rw = (k * w + 31) // 32
-    cap = max(w * rw, 1)
-    surv = (ctypes.c_int * max(k, 1))()
-    rows = (ctypes.c_uint32 * cap)()
-    _lib.check(lib.leoec_scrub_bitrows(_cid(coding), k, m, w, block, surv, rows, cap))
-    return list(surv[:k]), [list(rows[r * rw:(r + 1) * rw]) for r in range(w)]
+    return _bit_rows("leoec_scrub_bitrows", coding, params, block)
 
 
 def scrub_gfw_workspace(coding, params, size, nobj):
@@ -394,11 +395,7 @@ def scrub_gfw_workspace(coding, params, size, nobj):
     one pass over the batch: scrub_ws_workspace()'s for everything scrub_ws()
     serves; for the GF(2^w) word classes the header, one index word per object
     and the encode region of ``nobj`` objects."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_scrub_gfw_dev_workspace(_cid(coding), k, m, w, size, nobj,
-                                                 ctypes.byref(out)))
-    return out.value
+    return _query("scrub_gfw", coding, params, size, nobj)
 
 
 def scrub_gfw(coding, params, objs, size, parity, nobj=None, report=None, totals=None,
@@ -411,30 +408,8 @@ def scrub_gfw(coding, params, objs, size, parity, nobj=None, report=None, totals
     ``VERIFY_WORKSPACE_CAP`` (a smaller workspace than ``scrub_gfw_workspace()``
     gives the same results in more chunks of objects), and required on an
     explicit ``stream``."""
-    k, m, w, nobj, bs = _batch(coding, params, objs, size, parity, nobj)
-    if report is None:
-        report = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    if totals is None:
-        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
-    _words(report, nobj, "report")
-    _words(totals, 2, "totals")
-    need = scrub_gfw_workspace(coding, params, size, nobj)
-    if workspace is None:
-        head = 16 + (4 * nobj + 15) // 16 * 16
-        if stream is not None:
-            raise ValueError("scrub_gfw on an explicit stream needs an explicit workspace "
-                             f"({need} B for one pass)")
-        enc = need - head  # 0 for everything scrub() serves
-        if enc:
-            enc = max(min(enc, VERIFY_WORKSPACE_CAP), m * bs)
-        workspace = torch.empty(head + enc, dtype=torch.uint8, device=objs.device)
-    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("workspace: contiguous uint8 device tensor expected")
-    _lib.check(lib.leoec_scrub_gfw_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
-                                       size, nobj, parity.data_ptr(), _row_stride(parity),
-                                       report.data_ptr(), totals.data_ptr(), workspace.data_ptr(),
-                                       workspace.numel(), _stream(stream)))
-    return report, totals
+    return _scrub("scrub_gfw", coding, params, objs, size, parity, nobj, report, totals, workspace,
+                  stream)
 
 
 def scrub_wrows(coding, params, block):
@@ -443,21 +418,13 @@ def scrub_wrows(coding, params, block):
     coef)``: the k survivor ids (the first k ids ascending without ``block``)
     and the k GF(2^w) coefficients that give ``block`` from those survivors in
     that order."""
-    k, m, w = params
-    surv = (ctypes.c_int * max(k, 1))()
-    coef = (ctypes.c_uint32 * max(k, 1))()
-    _lib.check(lib.leoec_scrub_wrows(_cid(coding), k, m, w, block, surv, coef, max(k, 1)))
-    return list(surv[:k]), list(coef[:k])
+    return _word_rows("leoec_scrub_wrows", coding, params, block)
 
 
 def heal_ws_workspace(coding, params, size, nobj):
     """leoec_heal_ws_dev_workspace: bytes of workspace heal_ws() needs for
     ``nobj`` objects (a 16-byte header and one index word per object)."""
-    k, m, w = params
-    out = ctypes.c_uint64(0)
-    _lib.check(lib.leoec_heal_ws_dev_workspace(_cid(coding), k, m, w, size, nobj,
-                                               ctypes.byref(out)))
-    return out.value
+    return _query("heal_ws", coding, params, size, nobj)
 
 
 def heal_ws(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, totals=None,
@@ -471,24 +438,15 @@ def heal_ws(coding, params, objs, size, parity, lost, nobj=None, unhealed=None, 
     when not given; a call on an explicit ``stream`` must be given the
     workspace, for verify()'s reason."""
     k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
-    if unhealed is None:
-        unhealed = torch.empty(nobj, dtype=torch.int32, device=objs.device)
-    if totals is None:
-        totals = torch.empty(2, dtype=torch.int32, device=objs.device)
-    _words(lost, nobj, "lost")
-    _words(unhealed, nobj, "unhealed")
-    _words(totals, 2, "totals")
-    need = heal_ws_workspace(coding, params, size, nobj)
-    if workspace is None:
-        if stream is not None:
-            raise ValueError(f"heal_ws on an explicit stream needs an explicit workspace ({need} B)")
-        workspace = torch.empty(need, dtype=torch.uint8, device=objs.device)
-    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
-        raise ValueError("workspace: contiguous uint8 device tensor expected")
+    unhealed, totals = _int32(objs.device, [(unhealed, nobj, "unhealed"), (totals, 2, "totals")],
+                              [(lost, nobj, "lost")])
+    need = _query("heal_ws", coding, params, size, nobj)
+    ws_ptr, ws_bytes = _workspace_args(
+        _fixed_workspace("heal_ws", workspace, need, objs.device, stream))
     _lib.check(lib.leoec_heal_ws_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs),
                                      size, nobj, parity.data_ptr(), _row_stride(parity),
                                      lost.data_ptr(), unhealed.data_ptr(), totals.data_ptr(),
-                                     workspace.data_ptr(), workspace.numel(), _stream(stream)))
+                                     ws_ptr, ws_bytes, _stream(stream)))
     return unhealed, totals
 
 
@@ -516,13 +474,7 @@ def heal_bitrows(coding, params, mask, r):
     survivor ids (the first k intact ids ascending) and w lists of
     ``ceil(k w / 32)`` words, bit ``i w + c`` of row t set iff packet c of
     block ``surv[i]`` feeds packet t of the lost block."""
-    k, m, w = params
-    rw = (k * w + 31) // 32
-    cap = max(w * rw, 1)
-    surv = (ctypes.c_int * max(k, 1))()
-    rows = (ctypes.c_uint32 * cap)()
-    _lib.check(lib.leoec_heal_bitrows(_cid(coding), k, m, w, mask, r, surv, rows, cap))
-    return list(surv[:k]), [list(rows[t * rw:(t + 1) * rw]) for t in range(w)]
+    return _bit_rows("leoec_heal_bitrows", coding, params, mask, r)
 
 
 def heal_wrows(coding, params, mask, r):
@@ -531,11 +483,7 @@ def heal_wrows(coding, params, mask, r):
     outside heal()'s one-launch family.  Returns ``(surv, coef)``: the k
     survivor ids (the first k intact ids ascending) and the k GF(2^w)
     coefficients that give the lost block from them."""
-    k, m, w = params
-    surv = (ctypes.c_int * max(k, 1))()
-    coef = (ctypes.c_uint32 * max(k, 1))()
-    _lib.check(lib.leoec_heal_wrows(_cid(coding), k, m, w, mask, r, surv, coef, max(k, 1)))
-    return list(surv[:k]), list(coef[:k])
+    return _word_rows("leoec_heal_wrows", coding, params, mask, r)
 
 
 def locate_bitrows(coding, params):

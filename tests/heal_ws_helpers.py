@@ -22,7 +22,7 @@ REFUSED = [("vandrs", 16, 15, 8)]
 
 
 def sizes(family):
-    """scrub_gfw_helpers.sizes: k B - 1, 16 w (k - 2) + 5 and k B."""
+    """scrub_dev_helpers.sizes_and_whole: k B - 1, 16 w (k - 2) + 5 and k B."""
     cls, k, m, w, B = family
     return [k * B - 1, 16 * w * (k - 2) + 5, k * B]
 

@@ -10,7 +10,7 @@ configurations, one per K, and nothing else:
   m = 2 + (K - 1) % 3 (scrub needs m >= 2), vandrs for odd K and isars for even K
 
 Per configuration and size (4224 k - 3 and 128 (k - 1) + 5, the sizes of
-test_gf8_instances.py) two calls through scrub_dev_helpers.check_scrub, every
+test_gf8_instances.py) two calls through scrub_dev_helpers.SCRUB.check_scrub, every
 byte against the oracle's snapshot: scrub_helpers' whole-block batch (every
 valid byte of block b damaged in object b) and its position batch (64 values
 at the block's first byte or in its last partial tile).  After each call the
@@ -79,7 +79,7 @@ def main():
             batches.append(("positions", case, L.damaged_arenas(torch, case, dmg), want, skip))
             for name, case, (work, par), want, skip in batches:
                 keep = []
-                report, es = D.check_scrub(torch, le, case, work, par, want, skip, keep=keep)
+                report, es = D.SCRUB.check_scrub(torch, le, case, work, par, want, skip, keep=keep)
                 errs += [f"{name}: {e}" for e in es]
                 # (the report's own words: the object left out of the comparison is listed by its)
                 path = D.path(torch, keep[0], D._u32(report)[1:-1])

@@ -27,7 +27,7 @@ Two sizes each: k B - 1 with B = 1,040 w (one whole 1 KiB tile and a 16-byte
 partial one per packet, the last block one byte short) and, for k >= 2,
 16 w (k - 1) + 5 (packets of 16 bytes: a single tile with 63 lanes outside the
 packet, the last block 5 bytes).  Per configuration and size two calls through
-scrub_ws_helpers.check_scrub, every byte against the oracle's snapshot:
+scrub_dev_helpers.SCRUB_WS.check_scrub, every byte against the oracle's snapshot:
 scrub_helpers' whole-block batch (every valid byte of block b damaged in object
 b) and its position batch.  After each call the workspace must hold
 scrub_finish's list (scrub_dev_helpers.path): the rebuild was bit_heal_list's.
@@ -90,8 +90,8 @@ def main(name):
     import gpu_helpers as H
     import locate_helpers as L
     import scrub_dev_helpers as D
+    X = D.SCRUB_WS
     import scrub_helpers as S
-    import scrub_ws_helpers as X
 
     oracle.lib()
     group = GROUPS[name]

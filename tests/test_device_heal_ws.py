@@ -4,8 +4,6 @@ compared, unhealed between sentinels, lost unchanged), the totals, the
 workspace's tail, and objs / parity / unhealed byte for byte against a
 leoec_heal_dev run over clones of the same damaged arenas
 (heal_ws_helpers.run_heal_ws)."""
-import contextlib
-import ctypes
 import json
 import os
 import subprocess
@@ -17,6 +15,7 @@ import pytest
 import gpu_helpers as H
 import heal_helpers as HH
 import heal_ws_helpers as X
+import pending_helpers as PE
 import stream_helpers as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -220,50 +219,6 @@ def test_device_heal_ws_on_side_stream(gpu, le, oracle, fam):
 # hipSetDevice(-1) through the library's own runtime handle, no torch call
 # between planting and the clear).
 
-HIP_SUCCESS, HIP_ERROR_INVALID_DEVICE = 0, 101
-
-
-class _Wrapped:
-    """device.py's `lib` with leoec_heal_ws_dev wrapped."""
-
-    def __init__(self, real, call):
-        self._real, self._call = real, call
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        return self._call(fn) if name == "leoec_heal_ws_dev" else fn
-
-
-@contextlib.contextmanager
-def _planted(gpu, le, calls):
-    rt = ctypes.CDLL(le._lib.library_path())
-    for f in (rt.hipSetDevice, rt.hipPeekAtLastError, rt.hipGetLastError):
-        f.restype = ctypes.c_int
-    rt.hipSetDevice.argtypes = [ctypes.c_int]
-
-    def wrap(fn):
-        def call(*args):
-            gpu.cuda.synchronize()  # every buffer allocated and filled: no torch call from here
-            try:
-                assert rt.hipSetDevice(-1) == HIP_ERROR_INVALID_DEVICE
-                assert rt.hipPeekAtLastError() == HIP_ERROR_INVALID_DEVICE
-                rc = fn(*args)
-                calls.append((rc, rt.hipPeekAtLastError()))
-            finally:
-                rt.hipGetLastError()
-            return rc
-        return call
-
-    dev = le.device
-    real = dev.lib
-    dev.lib = _Wrapped(real, wrap)
-    try:
-        yield rt
-    finally:
-        dev.lib = real
-        rt.hipGetLastError()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("fam", STREAM_FAMILIES, ids=HH.family_id)
 def test_device_heal_ws_with_pending_error(gpu, le, oracle, fam):
@@ -275,11 +230,11 @@ def test_device_heal_ws_with_pending_error(gpu, le, oracle, fam):
     first = X.run_heal_ws(gpu, le, case, masks, reference=False)
     assert not first, "\n".join(first)
     calls = []
-    with _planted(gpu, le, calls) as rt:
+    with PE.planted(gpu, le, calls, "leoec_heal_ws_dev") as rt:
         errors = X.run_heal_ws(gpu, le, case, list(reversed(masks)), reference=False)
-    assert calls == [(0, HIP_ERROR_INVALID_DEVICE)], calls
+    assert calls == [(0, PE.HIP_ERROR_INVALID_DEVICE)], calls
     assert not errors, "\n".join(errors)
-    assert rt.hipPeekAtLastError() == HIP_SUCCESS
+    assert rt.hipPeekAtLastError() == PE.HIP_SUCCESS
 
 
 # ---------------------------------------------------------------------------

@@ -30,9 +30,12 @@ import gpu_helpers as H
 import locate_helpers as L
 import scrub_dev_helpers as D
 import scrub_helpers as S
+import stream_helpers as T
+
+X = D.SCRUB
 
 
-@pytest.fixture(scope="module", params=L.FAMILIES, ids=L.family_id)
+@pytest.fixture(scope="module", params=X.FAMILIES, ids=X.family_id)
 def family(request):
     """(module scope: the tests of one family run together and share its
     EdgeCases, the oracle's blocks computed once per size)"""
@@ -40,7 +43,7 @@ def family(request):
 
 
 def test_family_table():
-    assert len(L.FAMILIES) == 6
+    assert X.FAMILIES is L.FAMILIES and len(L.FAMILIES) == 6
     assert ("vandrs", 10, 4, 8, 164992) in L.FAMILIES and ("vandrs", 16, 4, 8, 8704) in L.FAMILIES
     assert any(f[2] == 2 for f in L.FAMILIES)  # the m = 2 limit is met
 
@@ -53,22 +56,18 @@ def test_device_scrub_positions(gpu, le, oracle, family):
     device.heal: identical arenas and words, no object left out.  Then a second
     scrub of the healed arenas: all zero but for the two-block object, nothing
     rebuilt, no byte changed."""
-    cls, k, m, w, B = family
     errors = []
-    for case in D.position_cases(le, oracle, family):
-        dmg, _, locate = S.position_batch(case)
-        want = S.two_block_word(oracle, le, case, dmg, locate)
-        skip = None if want[-1] == S.MANY else case.n - 1
-        assert skip is None or m == 2
+    for case in X.cases(le, oracle, family):
+        dmg, want, skip = X.position(le, oracle, case)
         work, par = L.damaged_arenas(gpu, case, dmg)
-        errors += D.check_scrub(gpu, le, case, work, par, want, skip)[1]
-        work, par, got, errs = D.check_equivalence(gpu, le, case, dmg)
+        errors += X.check_scrub(gpu, le, case, work, par, want, skip)[1]
+        work, par, got, _, errs = X.check_equivalence(gpu, le, case, dmg)
         errors += errs
         if got != want:
             errors.append(f"{case.ident()}: equivalence run's report {[hex(x) for x in got]}")
         # the healed arenas again
         healed, par_healed = work.clone(), par.clone()
-        _, again, tot, errs = D.run_scrub(gpu, le, case, work, par)
+        _, again, tot, errs = X.run_scrub(gpu, le, case, work, par)
         errors += errs
         ctx = f"second scrub {case.ident()} bs {case.bs}"
         # (m = 2 with a third block named: the other k + 1 blocks fit one
@@ -89,9 +88,9 @@ def test_device_scrub_positions(gpu, le, oracle, family):
 def test_device_scrub_clean_batch(gpu, le, oracle, family):
     """Nothing damaged: every word 0, totals (0, 0), no byte written."""
     errors = []
-    for case in D.position_cases(le, oracle, family):
+    for case in X.cases(le, oracle, family):
         work, par = L.damaged_arenas(gpu, case, [])
-        errors += D.check_scrub(gpu, le, case, work, par, [0] * case.n)[1]
+        errors += X.check_scrub(gpu, le, case, work, par, [0] * case.n)[1]
     assert not errors, "\n".join(errors[:20])
 
 
@@ -100,11 +99,11 @@ def test_device_scrub_dense_batch(gpu, le, oracle, family):
     """Every object with one damaged block, object o block o mod (k + m): every
     one named and rebuilt, and the two-call sequence leaves the same bytes."""
     errors = []
-    for case in D.position_cases(le, oracle, family):
+    for case in X.cases(le, oracle, family):
         dmg, want = D.dense_batch(case)
         work, par = L.damaged_arenas(gpu, case, dmg)
-        errors += D.check_scrub(gpu, le, case, work, par, want)[1]
-        errors += D.check_equivalence(gpu, le, case, dmg)[3]
+        errors += X.check_scrub(gpu, le, case, work, par, want)[1]
+        errors += X.check_equivalence(gpu, le, case, dmg)[4]
     assert not errors, "\n".join(errors[:20])
 
 
@@ -114,8 +113,8 @@ def test_device_scrub_whole_blocks(gpu, le, oracle, family):
     beside device.locate + device.heal, both back to the snapshot byte for
     byte; the rebuild was gf8_heal_list's (the list in the workspace)."""
     errors = []
-    for case in D.whole_cases(le, oracle, family):
-        path, errs = D.check_whole(gpu, le, case, S.whole_batch(case))
+    for case in X.whole_cases(le, oracle, family):
+        path, errs = X.check_whole(gpu, le, case, S.whole_batch(case))
         errors += errs
         if path != "list":
             errors.append(f"{case.ident()}: not the kernel path (more than 16 heal tables in this "
@@ -123,14 +122,11 @@ def test_device_scrub_whole_blocks(gpu, le, oracle, family):
     assert not errors, "\n".join(errors[:20])
 
 
-# gf8_heal_list's grid, restated: compute units x resident workgroups
-# (scrub_impl.hpp: 4 SIMDs of kGf8HealWaves waves, wg / 64 waves a workgroup)
+# gf8_heal_list's grid, restated (scrub_dev_helpers.SCRUB.resident): compute
+# units x resident workgroups (scrub_impl.hpp: 4 SIMDs of kGf8HealWaves waves,
+# wg / 64 waves a workgroup)
 GF8_HEAL_WAVES = 4
 LARGE = ("vandrs", 4, 2, 8, 4224)  # 256 lanes: a full 4,096-byte tile and a 128-byte one
-
-
-def gf8_heal_list_resident(wg):
-    return 4 * GF8_HEAL_WAVES * 64 // wg
 
 
 def test_grid_constants_are_the_sources():
@@ -151,7 +147,7 @@ def test_grid_constants_are_the_sources():
                      r"grid = grid < all \? grid : all;\s*"
                      r"if \(cap != 0u && grid > cap\) grid = cap;\s*"
                      r"return \(uint32_t\)grid;\s*\}", heal)
-    assert gf8_heal_list_resident(256) == 4 and gf8_heal_list_resident(64) == 16
+    assert [X.resident(wg) for wg in (256, 64)] == [4 * GF8_HEAL_WAVES * 64 // 256, 4 * GF8_HEAL_WAVES] == [4, 16]
     cls, k, m, w, B = LARGE
     assert B <= 160 * 1024 and -(-B // 4096) == 2  # the 256-lane form, two tiles a block
 
@@ -164,17 +160,17 @@ def test_device_scrub_batch_larger_than_the_grid(gpu, le, oracle):
     oracle's snapshot."""
     cls, k, m, w, B = LARGE
     cus = gpu.cuda.get_device_properties(gpu.cuda.current_device()).multi_processor_count
-    grid = cus * gf8_heal_list_resident(256)
-    tiles = -(-B // 4096)
-    n = -(-2 * grid // tiles)
+    tiles = -(-B // X.TILE)
+    n = -(-2 * cus * X.resident(256) // tiles)
+    grid = X.grid(cus, n, tiles, 0, 256)
     case = H.EdgeCase(le, oracle, LARGE[:4], k * B - 1, n)
-    assert case.bs == B and n * tiles >= 2 * grid
+    assert case.bs == B and n * tiles >= 2 * grid and grid == cus * X.resident(256)
     blocks = S.whole_dense_batch(case)
     want = S.whole_words(case, blocks)
     assert all(x == 1 << (o % (k + m)) for o, x in enumerate(want))  # no object left out
     work, par = S.whole_arenas(gpu, case, blocks)
     keep = []
-    errors = D.check_scrub(gpu, le, case, work, par, want, keep=keep)[1]
+    errors = X.check_scrub(gpu, le, case, work, par, want, keep=keep)[1]
     assert not errors, "\n".join(e[:2000] for e in errors[:20])
     assert D.path(gpu, keep[0], want) == "list"
 
@@ -185,53 +181,63 @@ def test_device_scrub_captured(gpu, le, oracle):
     into a graph (after one plain call, which builds heal's table and loads
     the code objects) it replays to the same report, totals and arenas, and
     again after the buffers are refilled with a differently damaged batch."""
-    family = L.FAMILIES[0]
-    cls, k, m, w, B = family
-    case = next(iter(D.position_cases(le, oracle, family)))
-    n, g = case.n, case.guard
-    snap, par_snap = case.dev(gpu)
-    dmg, _, locate = S.position_batch(case)
-    want = S.two_block_word(oracle, le, case, dmg, locate)
-    assert want[-1] == S.MANY  # m >= 3: every word by construction
-    first, par_first = L.damaged_arenas(gpu, case, dmg)
-    work, par = first.clone(), par_first.clone()
-    errors = D.check_scrub(gpu, le, case, work, par, want)[1]
+    case = next(iter(X.cases(le, oracle, X.FAMILIES[0])))
+    dmg, want, skip = X.position(le, oracle, case)
+    assert skip is None and want[-1] == S.MANY  # m >= 3: every word by construction
+    first = L.damaged_arenas(gpu, case, dmg)
+    errors = X.check_scrub(gpu, le, case, first[0].clone(), first[1].clone(), want)[1]
     assert not errors, "\n".join(errors)
-
-    def expect(before, par_before, words):
-        o_want, p_want = snap.clone(), par_snap.clone()
-        for o, word in enumerate(words):
-            if word == S.MANY:
-                o_want[g + o], p_want[1 + o] = before[g + o], par_before[1 + o]
-        return o_want, p_want, [sum(1 for x in words if x not in (0, S.MANY)),
-                                sum(1 for x in words if x == S.MANY)]
-
-    work.copy_(first)
-    par.copy_(par_first)
-    report = gpu.full((n,), L.PREFILL, dtype=gpu.int32, device="cuda")
-    totals = gpu.full((2,), D.TOTALS_PREFILL, dtype=gpu.int32, device="cuda")
-    need = le.device.scrub_workspace(cls, case.params, case.size, n)
-    ws = gpu.full((need,), D.WS_FILL, dtype=gpu.uint8, device="cuda")
-    gpu.cuda.synchronize()
-    graph = gpu.cuda.CUDAGraph()
-    with gpu.cuda.graph(graph):
-        le.device.scrub(cls, case.params, work[g:g + n], case.size, par[1:1 + n], report=report,
-                        totals=totals, workspace=ws)
     dense, dense_words = D.dense_batch(case)
-    second, par_second = L.damaged_arenas(gpu, case, dense)
-    for before, par_before, words in ((first, par_first, want), (second, par_second, dense_words),
-                                      (first, par_first, want)):
-        work.copy_(before)
-        par.copy_(par_before)
-        report.fill_(L.PREFILL)
-        totals.fill_(D.TOTALS_PREFILL)
-        graph.replay()
-        gpu.cuda.synchronize()
-        o_want, p_want, counts = expect(before, par_before, words)
-        assert D._u32(report) == words, [hex(x) for x in D._u32(report)]
-        assert D._u32(totals) == counts
-        assert not H.arena_diff(gpu, work, o_want, g, "replay: objs")
-        assert not H.arena_diff(gpu, par, p_want, 1, "replay: parity")
+    second = L.damaged_arenas(gpu, case, dense)
+    b = D.Buffers(X, gpu, le, case)
+    cap = T.Captured(gpu, b.call, lambda: b.refill(first), lambda: b.untouched(first))
+    errors = cap.errors
+    for r, (before, words) in enumerate(((first, want), (second, dense_words), (first, want))):
+        b.refill(before)
+        cap.replay()
+        errors += b.check(before, words, f"captured scrub {case.ident()} replay {r}")
+    assert not errors, "\n".join(errors[:20])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("call", D.CALLS, ids=lambda c: c.name)
+def test_harness_reports_a_wrong_word_and_an_unexpected_object(gpu, le, oracle, call):
+    """check_scrub must fail when it should.  The position batch of the call's
+    first family at 16 w (k - 2) + 5 through a correct call, (a) against
+    expectations with one word changed to a single-bit word: the two-block
+    object's, so the object shows in the report, in the totals and, left as it
+    was damaged where the expectations have it rebuilt, in both arenas; and
+    one rebuilt object's, to another block: the report alone, since the counts
+    and the bytes are the same; (b) with the clean object damaged as well,
+    which the expectations do not know: a report error naming it."""
+    family = call.FAMILIES[0]
+    cls, k, m, w, B = family
+    case = next(iter(call.cases(le, oracle, family, [16 * w * (k - 2) + 5])))
+    n, two = case.n, case.n - 1
+    dmg, want, skip = call.position(le, oracle, case)
+    assert n == k + m + 2 and skip is None
+    assert want[1] == 2 and want[k + m] == 0 and want[two] == S.MANY and D.counts(want) == [k + m - 1, 1]
+
+    def errors_of(dmg, words):
+        work, par = L.damaged_arenas(gpu, case, dmg)
+        return call.check_scrub(gpu, le, case, work, par, words)[1]
+
+    assert errors_of(dmg, want) == []
+    # (a) the two-block object expected with block 0 named and rebuilt
+    errors = errors_of(dmg, want[:two] + [1])
+    assert len(errors) == 4, errors
+    assert f"{call.name} {case.ident()}" in errors[0] and f"objects [{two}]: report" in errors[0]
+    assert f"totals [{k + m - 1}, 1], expected [{k + m}, 0]" in errors[1]
+    assert ": objs: " in errors[2] and f"in rows [{two}] " in errors[2]
+    assert ": parity: " in errors[3] and f"in rows [{two}] " in errors[3]
+    # object 1 expected with block 2 named: the same counts, the same bytes
+    errors = errors_of(dmg, [want[0], 4] + want[2:])
+    assert len(errors) == 1 and "objects [1]: report" in errors[0], errors
+    # (b) the clean object k + m has block 0 damaged too
+    errors = errors_of(dmg + S._entries(case, k + m, 0, S.VALUES[:S.HITS]), want)
+    assert len(errors) == 2, errors
+    assert f"objects [{k + m}]: report" in errors[0]
+    assert f"totals [{k + m}, 1], expected [{k + m - 1}, 1]" in errors[1]
 
 
 @pytest.mark.gpu
@@ -244,7 +250,7 @@ def test_scrub_with_full_table_cache_in_own_process(gpu, tmp_path):
     log = str(tmp_path / "scrub_table_cache.log")
     env = dict(os.environ, LIBC_FATAL_STDERR_="1")
     env.pop("LEOEC_LIBRARY", None)
-    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_table_cache_child.py")]
+    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_table_cache_child.py"), "scrub"]
     with open(log, "w") as fh:
         rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=280)
     with open(log) as fh:

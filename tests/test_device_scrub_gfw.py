@@ -9,7 +9,7 @@ report); the batches are test_device_scrub_ws.py's (scrub_helpers' position
 batch, a clean batch, scrub_dev_helpers' dense batch, scrub_helpers'
 whole-block batch), for the six word families of locate_gfw_helpers.FAMILIES
 with 8,704-byte blocks (two whole 4 KiB tiles and a 512-byte partial one) at
-the sizes k B - 1, 16 w (k - 2) + 5 and k B (scrub_gfw_helpers.sizes).
+the sizes k B - 1, 16 w (k - 2) + 5 and k B (scrub_dev_helpers.SCRUB_GFW.sizes).
 Expected words are by construction (test_scrub_gfw_cpu.py holds them against
 the host model).
 
@@ -20,8 +20,6 @@ valid byte of block b in object b: the result is right only if every tile,
 every lane, all four chunks, both store paths and the ragged tail were
 written.  The dense form of it in a batch of twice the launch's grid runs the
 kernel's loop into its second trip in the product library."""
-import contextlib
-import ctypes
 import os
 import subprocess
 import sys
@@ -32,14 +30,15 @@ import gpu_helpers as H
 import locate_gfw_helpers as G
 import locate_helpers as L
 import locate_ws_helpers as W
+import pending_helpers as PE
 import scrub_dev_helpers as D
-import scrub_gfw_helpers as X
 import scrub_helpers as S
-import scrub_ws_helpers as XW
 import stream_helpers as T
 
+X, XW = D.SCRUB_GFW, D.SCRUB_WS
 
-@pytest.fixture(scope="module", params=X.FAMILIES, ids=G.family_id)
+
+@pytest.fixture(scope="module", params=X.FAMILIES, ids=X.family_id)
 def family(request):
     """(module scope: the tests of one family run together and share its
     EdgeCases, the oracle's blocks computed once per size)"""
@@ -173,10 +172,10 @@ def test_device_scrub_gfw_batch_larger_than_the_grid(gpu, le, oracle):
     cls, k, m, w, B = LARGE
     cus = gpu.cuda.get_device_properties(gpu.cuda.current_device()).multi_processor_count
     tiles = -(-B // X.TILE)
-    n = -(-2 * cus * X.gfw_heal_list_resident() // tiles)
+    n = -(-2 * cus * X.resident() // tiles)
     grid = X.grid(cus, n, tiles)
     case = H.EdgeCase(le, oracle, LARGE[:4], k * B - 1, n)
-    assert case.bs == B and n * tiles >= 2 * grid and grid == cus * X.gfw_heal_list_resident()
+    assert case.bs == B and n * tiles >= 2 * grid and grid == cus * X.resident()
     blocks = S.whole_dense_batch(case)
     want = S.whole_words(case, blocks)
     assert all(x == 1 << (o % (k + m)) for o, x in enumerate(want))  # no object left out
@@ -216,8 +215,8 @@ def test_device_scrub_gfw_forwards_class_a(gpu, le, oracle, fam):
     errors = []
     for case in XW.cases(le, oracle, fam):
         n, g = case.n, case.guard
-        dmg, _, locate = S.position_batch(case)
-        want = S.two_block_word(oracle, le, case, dmg, locate)
+        dmg, want, skip = XW.position(le, oracle, case)
+        assert skip is None
         need = le.device.scrub_ws_workspace(case.cls, case.params, case.size, n)
         assert le.device.scrub_gfw_workspace(case.cls, case.params, case.size, n) == need
         work, par = L.damaged_arenas(gpu, case, dmg)
@@ -251,62 +250,6 @@ def _stream_case(le, oracle):
     return next(iter(X.cases(le, oracle, family)))
 
 
-class _Buffers:
-    """The work arenas, the words and the workspace of one call, refilled from
-    a damaged pair of arenas."""
-
-    def __init__(self, gpu, le, case):
-        self.gpu, self.le, self.case = gpu, le, case
-        n = case.n
-        snap, par_snap = case.dev(gpu)
-        self.work, self.par = gpu.zeros_like(snap), gpu.zeros_like(par_snap)
-        self.report = gpu.full((n + 2,), L.PREFILL, dtype=gpu.int32, device="cuda")
-        self.totals = gpu.full((4,), D.TOTALS_PREFILL, dtype=gpu.int32, device="cuda")
-        self.need = X.workspace_bytes(le, case)
-        self.ws = gpu.full((self.need + D.WS_TAIL,), D.WS_FILL, dtype=gpu.uint8, device="cuda")
-
-    def refill(self, src):
-        self.work.copy_(src[0])
-        self.par.copy_(src[1])
-        self.report.fill_(L.PREFILL)
-        self.report[0], self.report[-1] = L.SENTINELS
-        self.totals.fill_(D.TOTALS_PREFILL)
-        self.totals[0], self.totals[3] = L.SENTINELS
-
-    def call(self, stream=None):
-        case, n, g = self.case, self.case.n, self.case.guard
-        self.le.device.scrub_gfw(case.cls, case.params, self.work[g:g + n], case.size,
-                                 self.par[1:1 + n], report=self.report[1:1 + n],
-                                 totals=self.totals[1:3], workspace=self.ws[:self.need], stream=stream)
-
-    def untouched(self, src):
-        """The errors of everything that no longer holds what refill put there."""
-        gpu, n = self.gpu, self.case.n
-        errors = T._diffs(gpu, [(self.work, src[0], self.case.guard, "objs"), (self.par, src[1], 1, "parity")])
-        if D._u32(self.report) != [L.SENTINELS[0]] + [L.PREFILL & 0xFFFFFFFF] * n + [L.SENTINELS[1]]:
-            errors.append("report written")
-        if D._u32(self.totals) != [L.SENTINELS[0]] + [D.TOTALS_PREFILL] * 2 + [L.SENTINELS[1]]:
-            errors.append("totals written")
-        return errors
-
-    def check(self, before, words, ctx):
-        gpu, case, g = self.gpu, self.case, self.case.guard
-        snap, par_snap = case.dev(gpu)
-        o_want, p_want = snap.clone(), par_snap.clone()
-        for o, word in enumerate(words):
-            if word == S.MANY:
-                o_want[g + o], p_want[1 + o] = before[0][g + o], before[1][1 + o]
-        errors = T._diffs(gpu, [(self.work, o_want, g, f"{ctx}: objs"), (self.par, p_want, 1, f"{ctx}: parity")])
-        got, tot = D._u32(self.report), D._u32(self.totals)
-        if got != [L.SENTINELS[0]] + list(words) + [L.SENTINELS[1]]:
-            errors.append(f"{ctx}: report {[hex(x) for x in got]} (first and last: sentinels)")
-        if tot != [L.SENTINELS[0]] + X.counts(words) + [L.SENTINELS[1]]:
-            errors.append(f"{ctx}: totals {[hex(x) for x in tot]} (first and last: sentinels)")
-        if not bool((self.ws[self.need:] == D.WS_FILL).all()):
-            errors.append(f"{ctx}: workspace written past its {self.need} bytes")
-        return errors
-
-
 @pytest.mark.gpu
 def test_device_scrub_gfw_captured(gpu, le, oracle):
     """The call is memsets and launches on the stream: after one plain call
@@ -320,7 +263,7 @@ def test_device_scrub_gfw_captured(gpu, le, oracle):
     first = L.damaged_arenas(gpu, case, dmg)
     dense, dense_words = D.dense_batch(case)
     second = L.damaged_arenas(gpu, case, dense)
-    b = _Buffers(gpu, le, case)
+    b = D.Buffers(X, gpu, le, case)
     cap = T.Captured(gpu, b.call, lambda: b.refill(first), lambda: b.untouched(first))
     errors = cap.errors
     for r, (before, words) in enumerate(((first, want), (second, dense_words), (first, want))):
@@ -338,7 +281,7 @@ def test_device_scrub_gfw_on_side_stream(gpu, le, oracle):
     case = _stream_case(le, oracle)
     dmg, want, skip = X.position(le, oracle, case)
     src = L.damaged_arenas(gpu, case, dmg)
-    b = _Buffers(gpu, le, case)
+    b = D.Buffers(X, gpu, le, case)
     b.refill(src)
     b.call()
     gpu.cuda.synchronize()
@@ -362,50 +305,6 @@ def test_device_scrub_gfw_on_side_stream(gpu, le, oracle):
 # hipSetDevice(-1) through the library's own runtime handle, no torch call
 # between planting and the clear).
 
-HIP_SUCCESS, HIP_ERROR_INVALID_DEVICE = 0, 101
-
-
-class _Wrapped:
-    """device.py's `lib` with leoec_scrub_gfw_dev wrapped."""
-
-    def __init__(self, real, call):
-        self._real, self._call = real, call
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        return self._call(fn) if name == "leoec_scrub_gfw_dev" else fn
-
-
-@contextlib.contextmanager
-def _planted(gpu, le, calls):
-    rt = ctypes.CDLL(le._lib.library_path())
-    for f in (rt.hipSetDevice, rt.hipPeekAtLastError, rt.hipGetLastError):
-        f.restype = ctypes.c_int
-    rt.hipSetDevice.argtypes = [ctypes.c_int]
-
-    def wrap(fn):
-        def call(*args):
-            gpu.cuda.synchronize()  # every buffer allocated and filled: no torch call from here
-            try:
-                assert rt.hipSetDevice(-1) == HIP_ERROR_INVALID_DEVICE
-                assert rt.hipPeekAtLastError() == HIP_ERROR_INVALID_DEVICE
-                rc = fn(*args)
-                calls.append((rc, rt.hipPeekAtLastError()))
-            finally:
-                rt.hipGetLastError()
-            return rc
-        return call
-
-    dev = le.device
-    real = dev.lib
-    dev.lib = _Wrapped(real, wrap)
-    try:
-        yield rt
-    finally:
-        dev.lib = real
-        rt.hipGetLastError()
-
-
 @pytest.mark.gpu
 def test_device_scrub_gfw_with_pending_error(gpu, le, oracle):
     """A first plain call, then one with hipErrorInvalidDevice pending on the
@@ -422,17 +321,17 @@ def test_device_scrub_gfw_with_pending_error(gpu, le, oracle):
     want = [1 << (k + o) for o in range(3)]
     work, par = L.damaged_arenas(gpu, case, dmg)
     calls = []
-    with _planted(gpu, le, calls) as rt:
+    with PE.planted(gpu, le, calls, "leoec_scrub_gfw_dev") as rt:
         errors = X.check_scrub(gpu, le, case, work, par, want)[1]
-    assert calls == [(0, HIP_ERROR_INVALID_DEVICE)], calls
+    assert calls == [(0, PE.HIP_ERROR_INVALID_DEVICE)], calls
     assert not errors, "\n".join(errors)
-    assert rt.hipPeekAtLastError() == HIP_SUCCESS
+    assert rt.hipPeekAtLastError() == PE.HIP_SUCCESS
 
 
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_scrub_gfw_with_full_table_cache_in_own_process(gpu, tmp_path):
-    """tests/scrub_gfw_table_cache_child.py in a fresh process: 16 word
+    """tests/scrub_table_cache_child.py scrub_gfw in a fresh process: 16 word
     configurations scrubbed first fill the block table cache, the scrub of a
     17th then takes the composed path and must still equal locate_gfw + heal
     byte for byte."""
@@ -440,12 +339,12 @@ def test_scrub_gfw_with_full_table_cache_in_own_process(gpu, tmp_path):
     log = str(tmp_path / "scrub_gfw_table_cache.log")
     env = dict(os.environ, LIBC_FATAL_STDERR_="1")
     env.pop("LEOEC_LIBRARY", None)
-    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_gfw_table_cache_child.py")]
+    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_table_cache_child.py"), "scrub_gfw"]
     with open(log, "w") as fh:
         rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=280)
     with open(log) as fh:
         tail = fh.read()[-4000:]
-    assert rc == 0, f"scrub_gfw_table_cache_child.py failed (rc {rc}), {log}:\n{tail}"
+    assert rc == 0, f"scrub_table_cache_child.py scrub_gfw failed (rc {rc}), {log}:\n{tail}"
     assert "17th configuration scrubbed" in tail, tail
 
 
@@ -469,11 +368,11 @@ def _wide_plan(le, oracle, variant):
     p.outputs = Wd._damage(lay, case, p.pre, blocks)
     want = S.whole_words(case, blocks)
     assert G.words_of(oracle, le, case, S.whole_objects(case, blocks)) == want
-    assert X.counts(want) == [2, 0]
+    assert D.counts(want) == [2, 0]
     p.words_pre = {"report": Wd._sentinels([L.PREFILL] * Wd.NOBJ, L.SENTINELS),
                    "totals": Wd._sentinels([D.TOTALS_PREFILL] * 2, L.SENTINELS)}
     p.words_want = {"report": Wd._sentinels(want, L.SENTINELS),
-                    "totals": Wd._sentinels(X.counts(want), L.SENTINELS),
+                    "totals": Wd._sentinels(D.counts(want), L.SENTINELS),
                     "workspace tail": Wd.WS_TAIL_WANT}
     need = X.workspace_bytes(le, case, 1 if variant == "min" else None)
 

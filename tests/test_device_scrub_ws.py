@@ -12,7 +12,7 @@ bitmatrix families of locate_ws_helpers.FAMILIES at the sizes k B - 1 and
 16 w (k - 2) + 5 (every packet has whole 1 KiB tiles and a last partial one,
 the last data block is ragged at the first size, empty with the one before it
 ragged at the second) and at k B, where no block is clipped
-(scrub_ws_helpers.cases).  Expected words are by construction.
+(scrub_dev_helpers.SCRUB_WS.sizes).  Expected words are by construction.
 
 Those batches damage at most 64 bytes of a block, 64 / w of a packet, all in
 lane 0's column of one tile: every other byte equals the snapshot whether
@@ -23,8 +23,6 @@ result is right only if every tile of every packet, every lane, both store
 paths and the ragged tail were written.  The dense form of it in a batch of
 twice the launch's grid runs the kernel's loop into its second trip in the
 product library."""
-import contextlib
-import ctypes
 import os
 import re
 import subprocess
@@ -36,11 +34,14 @@ import gpu_helpers as H
 import locate_helpers as L
 import locate_ws_helpers as W
 import scrub_dev_helpers as D
+import pending_helpers as PE
 import scrub_helpers as S
-import scrub_ws_helpers as X
+import stream_helpers as T
+
+X = D.SCRUB_WS
 
 
-@pytest.fixture(scope="module", params=W.FAMILIES, ids=W.family_id)
+@pytest.fixture(scope="module", params=X.FAMILIES, ids=X.family_id)
 def family(request):
     """(module scope: the tests of one family run together and share its
     EdgeCases, the oracle's blocks computed once per size)"""
@@ -49,14 +50,6 @@ def family(request):
 
 # every family's packet has whole 1 KiB tiles and a last partial one
 assert all(B // w > X.TILE and (B // w) % X.TILE != 0 for _, _, _, w, B in W.FAMILIES)
-
-
-def _position(le, oracle, case):
-    dmg, _, locate = S.position_batch(case)
-    want = S.two_block_word(oracle, le, case, dmg, locate)
-    skip = None if want[-1] == S.MANY else case.n - 1
-    assert skip is None or case.m == 2
-    return dmg, want, skip
 
 
 @pytest.mark.gpu
@@ -69,7 +62,7 @@ def test_device_scrub_ws_positions(gpu, le, oracle, family):
     nothing rebuilt, no byte changed."""
     errors = []
     for case in X.cases(le, oracle, family):
-        dmg, want, skip = _position(le, oracle, case)
+        dmg, want, skip = X.position(le, oracle, case)
         work, par = L.damaged_arenas(gpu, case, dmg)
         errors += X.check_scrub(gpu, le, case, work, par, want, skip)[1]
         work, par, got, _, errs = X.check_equivalence(gpu, le, case, dmg)
@@ -123,7 +116,7 @@ def test_device_scrub_ws_small_workspaces(gpu, le, oracle, family):
     and with room for 3 objects: report, totals and arenas as with one pass."""
     errors = []
     for case in X.cases(le, oracle, family):
-        dmg, want, skip = _position(le, oracle, case)
+        dmg, want, skip = X.position(le, oracle, case)
         ref_work, ref_par, ref_got, ref_tot, errs = X.check_equivalence(gpu, le, case, dmg)
         errors += errs
         for room in (1, 3):
@@ -166,11 +159,8 @@ def test_device_scrub_ws_whole_blocks(gpu, le, oracle, family):
 # (bit_heal_tile.hpp: one wave each, 32 waves a compute unit, w KiB of its
 # 160 KiB of LDS each)
 # (m = 3: neither side builds an m = 2 Cauchy matrix past w = 20)
+# (scrub_dev_helpers.SCRUB_WS.resident)
 LARGE = ("cauchyrs", 2, 3, 32, 1040 * 32)  # packets of 1,040 bytes: a full tile and a 16-byte one
-
-
-def bit_heal_list_resident(w):
-    return min(160 // w, 32)
 
 
 def test_grid_constants_are_the_sources(le, oracle):
@@ -191,7 +181,7 @@ def test_grid_constants_are_the_sources(le, oracle):
             in launch)
     assert "uint64_t grid = (uint64_t)device_cus() * resident;" in heal
     assert "grid = grid < all ? grid : all;" in heal
-    assert [bit_heal_list_resident(w) for w in (2, 5, 6, 17, 32)] == [32, 32, 26, 9, 5]
+    assert [X.resident(w) for w in (2, 5, 6, 17, 32)] == [32, 32, 26, 9, 5]
     cls, k, m, w, B = LARGE
     assert B % (16 * w) == 0 and -(-(B // w) // X.TILE) == 2 and W.served(cls, k, m, w)
     assert len(oracle.encode(cls, k, m, w, b"\x5a")) == k + m
@@ -207,11 +197,11 @@ def test_device_scrub_ws_batch_larger_than_the_grid(gpu, le, oracle):
     oracle's snapshot."""
     cls, k, m, w, B = LARGE
     cus = gpu.cuda.get_device_properties(gpu.cuda.current_device()).multi_processor_count
-    grid = cus * bit_heal_list_resident(w)
     tiles = -(-(B // w) // X.TILE)
-    n = -(-2 * grid // tiles)
+    n = -(-2 * cus * X.resident(w) // tiles)
+    grid = X.grid(cus, n, tiles, 0, w)
     case = H.EdgeCase(le, oracle, LARGE[:4], k * B - 1, n)
-    assert case.bs == B and n * tiles >= 2 * grid
+    assert case.bs == B and n * tiles >= 2 * grid and grid == cus * X.resident(w)
     blocks = S.whole_dense_batch(case)
     want = S.whole_words(case, blocks)
     assert all(x == 1 << (o % (k + m)) for o, x in enumerate(want))  # no object left out
@@ -230,15 +220,15 @@ def test_device_scrub_ws_forwards_the_fused_family(gpu, le, oracle):
     assert family in L.FAMILIES
     errors = []
     for case in X.cases(le, oracle, family):
-        dmg, _, locate = S.position_batch(case)
-        want = S.two_block_word(oracle, le, case, dmg, locate)
+        dmg, want, skip = X.position(le, oracle, case)
+        assert skip is None
         work, par = L.damaged_arenas(gpu, case, dmg)
         errors += X.check_scrub(gpu, le, case, work, par, want)[1]
         work, par = L.damaged_arenas(gpu, case, dmg)
         work2, par2 = work.clone(), par.clone()
         _, got, tot, errs = X.run_scrub(gpu, le, case, work, par)
         errors += errs
-        _, got2, tot2, errs = D.run_scrub(gpu, le, case, work2, par2)
+        _, got2, tot2, errs = D.SCRUB.run_scrub(gpu, le, case, work2, par2)
         errors += errs
         ctx = f"scrub_ws against scrub {case.ident()}"
         if (got, tot) != (got2, tot2):
@@ -257,103 +247,30 @@ def test_device_scrub_ws_captured(gpu, le, oracle):
     (after one plain call, which builds the block table and loads the code
     objects) it replays to the same report, totals and arenas, and again after
     the buffers are refilled with a differently damaged batch."""
-    family = W.FAMILIES[0]
-    cls, k, m, w, B = family
-    assert (cls, k, m, w) == ("cauchyrs", 10, 4, 8)
-    case = next(iter(D.position_cases(le, oracle, family)))
-    n, g = case.n, case.guard
-    snap, par_snap = case.dev(gpu)
-    dmg, want, skip = _position(le, oracle, case)
+    family = X.FAMILIES[0]
+    assert family[:4] == ("cauchyrs", 10, 4, 8)
+    case = next(iter(X.cases(le, oracle, family)))
+    dmg, want, skip = X.position(le, oracle, case)
     assert skip is None  # m >= 3: every word by construction
-    first, par_first = L.damaged_arenas(gpu, case, dmg)
-    work, par = first.clone(), par_first.clone()
-    errors = X.check_scrub(gpu, le, case, work, par, want)[1]
+    first = L.damaged_arenas(gpu, case, dmg)
+    errors = X.check_scrub(gpu, le, case, first[0].clone(), first[1].clone(), want)[1]
     assert not errors, "\n".join(errors)
-
-    def expect(before, par_before, words):
-        o_want, p_want = snap.clone(), par_snap.clone()
-        for o, word in enumerate(words):
-            if word == S.MANY:
-                o_want[g + o], p_want[1 + o] = before[g + o], par_before[1 + o]
-        return o_want, p_want, [sum(1 for x in words if x not in (0, S.MANY)),
-                                sum(1 for x in words if x == S.MANY)]
-
-    work.copy_(first)
-    par.copy_(par_first)
-    report = gpu.full((n,), L.PREFILL, dtype=gpu.int32, device="cuda")
-    totals = gpu.full((2,), D.TOTALS_PREFILL, dtype=gpu.int32, device="cuda")
-    need = le.device.scrub_ws_workspace(cls, case.params, case.size, n)
-    ws = gpu.full((need,), D.WS_FILL, dtype=gpu.uint8, device="cuda")
-    gpu.cuda.synchronize()
-    graph = gpu.cuda.CUDAGraph()
-    with gpu.cuda.graph(graph):
-        le.device.scrub_ws(cls, case.params, work[g:g + n], case.size, par[1:1 + n], report=report,
-                           totals=totals, workspace=ws)
     dense, dense_words = D.dense_batch(case)
-    second, par_second = L.damaged_arenas(gpu, case, dense)
-    for before, par_before, words in ((first, par_first, want), (second, par_second, dense_words),
-                                      (first, par_first, want)):
-        work.copy_(before)
-        par.copy_(par_before)
-        report.fill_(L.PREFILL)
-        totals.fill_(D.TOTALS_PREFILL)
-        graph.replay()
-        gpu.cuda.synchronize()
-        o_want, p_want, counts = expect(before, par_before, words)
-        assert D._u32(report) == words, [hex(x) for x in D._u32(report)]
-        assert D._u32(totals) == counts
-        assert not H.arena_diff(gpu, work, o_want, g, "replay: objs")
-        assert not H.arena_diff(gpu, par, p_want, 1, "replay: parity")
+    second = L.damaged_arenas(gpu, case, dense)
+    b = D.Buffers(X, gpu, le, case)
+    cap = T.Captured(gpu, b.call, lambda: b.refill(first), lambda: b.untouched(first))
+    errors = cap.errors
+    for r, (before, words) in enumerate(((first, want), (second, dense_words), (first, want))):
+        b.refill(before)
+        cap.replay()
+        errors += b.check(before, words, f"captured scrub_ws {case.ident()} replay {r}")
+    assert not errors, "\n".join(errors[:20])
 
 
 # ---------------------------------------------------------------------------
 # A HIP error pending on the calling thread (test_pending_hip_error.py's way:
 # hipSetDevice(-1) through the library's own runtime handle, no torch call
 # between planting and the clear).
-
-HIP_SUCCESS, HIP_ERROR_INVALID_DEVICE = 0, 101
-
-
-class _Wrapped:
-    """device.py's `lib` with leoec_scrub_ws_dev wrapped."""
-
-    def __init__(self, real, call):
-        self._real, self._call = real, call
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        return self._call(fn) if name == "leoec_scrub_ws_dev" else fn
-
-
-@contextlib.contextmanager
-def _planted(gpu, le, calls):
-    rt = ctypes.CDLL(le._lib.library_path())
-    for f in (rt.hipSetDevice, rt.hipPeekAtLastError, rt.hipGetLastError):
-        f.restype = ctypes.c_int
-    rt.hipSetDevice.argtypes = [ctypes.c_int]
-
-    def wrap(fn):
-        def call(*args):
-            gpu.cuda.synchronize()  # every buffer allocated and filled: no torch call from here
-            try:
-                assert rt.hipSetDevice(-1) == HIP_ERROR_INVALID_DEVICE
-                assert rt.hipPeekAtLastError() == HIP_ERROR_INVALID_DEVICE
-                rc = fn(*args)
-                calls.append((rc, rt.hipPeekAtLastError()))
-            finally:
-                rt.hipGetLastError()
-            return rc
-        return call
-
-    dev = le.device
-    real = dev.lib
-    dev.lib = _Wrapped(real, wrap)
-    try:
-        yield rt
-    finally:
-        dev.lib = real
-        rt.hipGetLastError()
-
 
 @pytest.mark.gpu
 def test_device_scrub_ws_with_pending_error(gpu, le, oracle):
@@ -370,17 +287,17 @@ def test_device_scrub_ws_with_pending_error(gpu, le, oracle):
     want = [1 << (k + o) for o in range(3)]
     work, par = L.damaged_arenas(gpu, case, dmg)
     calls = []
-    with _planted(gpu, le, calls) as rt:
+    with PE.planted(gpu, le, calls, "leoec_scrub_ws_dev") as rt:
         errors = X.check_scrub(gpu, le, case, work, par, want)[1]
-    assert calls == [(0, HIP_ERROR_INVALID_DEVICE)], calls
+    assert calls == [(0, PE.HIP_ERROR_INVALID_DEVICE)], calls
     assert not errors, "\n".join(errors)
-    assert rt.hipPeekAtLastError() == HIP_SUCCESS
+    assert rt.hipPeekAtLastError() == PE.HIP_SUCCESS
 
 
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_scrub_ws_with_full_table_cache_in_own_process(gpu, tmp_path):
-    """tests/scrub_ws_table_cache_child.py in a fresh process: 16 bitmatrix
+    """tests/scrub_table_cache_child.py scrub_ws in a fresh process: 16 bitmatrix
     configurations scrubbed first fill the block table cache, the scrub of a
     17th then takes the composed path and must still equal locate_ws + heal
     byte for byte."""
@@ -388,10 +305,10 @@ def test_scrub_ws_with_full_table_cache_in_own_process(gpu, tmp_path):
     log = str(tmp_path / "scrub_ws_table_cache.log")
     env = dict(os.environ, LIBC_FATAL_STDERR_="1")
     env.pop("LEOEC_LIBRARY", None)
-    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_ws_table_cache_child.py")]
+    cmd = [sys.executable, "-u", os.path.join(root, "tests", "scrub_table_cache_child.py"), "scrub_ws"]
     with open(log, "w") as fh:
         rc = subprocess.call(cmd, cwd=root, env=env, stdout=fh, stderr=subprocess.STDOUT, timeout=280)
     with open(log) as fh:
         tail = fh.read()[-4000:]
-    assert rc == 0, f"scrub_ws_table_cache_child.py failed (rc {rc}), {log}:\n{tail}"
+    assert rc == 0, f"scrub_table_cache_child.py scrub_ws failed (rc {rc}), {log}:\n{tail}"
     assert "17th configuration scrubbed" in tail, tail

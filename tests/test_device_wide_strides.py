@@ -55,7 +55,7 @@ import time
 import pytest
 
 import gpu_helpers as H
-import scrub_ws_helpers as X
+import scrub_dev_helpers as D
 import verify_helpers as V
 import wide_helpers as Wd
 import wide_strides_child as C
@@ -140,7 +140,7 @@ def test_wide_case_table(le, family):
     assert rc == (0 if "locate" in kinds else E_UNSUPPORTED)
     assert ("scrub" in kinds) == ("locate" in kinds)
     rc, need = _status(lambda: dev.scrub_workspace(cls, params, size, Wd.NOBJ))
-    assert (rc, need) == ((0, X.head(Wd.NOBJ)) if "scrub" in kinds else (E_UNSUPPORTED, None))
+    assert (rc, need) == ((0, D.head(Wd.NOBJ)) if "scrub" in kinds else (E_UNSUPPORTED, None))
     rc, _ = _status(lambda: dev.locate_bitrows(cls, params))
     assert rc == (0 if "locate_ws" in kinds else E_UNSUPPORTED)
     rc, need = _status(lambda: dev.locate_ws_workspace(cls, params, size, Wd.NOBJ))
@@ -150,9 +150,9 @@ def test_wide_case_table(le, family):
         assert (rc, need) == ((0, Wd.NOBJ * m * B) if "locate_ws" in kinds else (E_UNSUPPORTED, None))
     rc, need = _status(lambda: dev.scrub_ws_workspace(cls, params, size, Wd.NOBJ))
     if "scrub" in kinds:
-        assert (rc, need) == (0, X.head(Wd.NOBJ))
+        assert (rc, need) == (0, D.head(Wd.NOBJ))
     elif "scrub_ws" in kinds:
-        assert (rc, need) == (0, X.head(Wd.NOBJ) + Wd.NOBJ * m * B) and "locate_ws" in kinds
+        assert (rc, need) == (0, D.head(Wd.NOBJ) + Wd.NOBJ * m * B) and "locate_ws" in kinds
     else:
         assert rc == E_UNSUPPORTED and "locate_ws" not in kinds
 

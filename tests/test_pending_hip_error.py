@@ -216,14 +216,14 @@ def _scrub(gpu, le, oracle, hip, case):
     first: data blocks 0..2; the second: coding blocks 0..2)."""
     dmg, want = D.dense_batch(case)
     work, par = L.damaged_arenas(gpu, case, dmg)
-    _, first = D.check_scrub(gpu, le, case, work, par, want)
+    _, first = D.SCRUB.check_scrub(gpu, le, case, work, par, want)
     assert not first, "\n".join(first)
     k = case.k
     dmg = [e for o in range(N) for e in S._entries(case, o, k + o, S.VALUES[:S.HITS])]
     want = [1 << (k + o) for o in range(N)]
     work, par = L.damaged_arenas(gpu, case, dmg)
     with planted(gpu, le, hip, "leoec_scrub_dev") as calls:
-        _, errors = D.check_scrub(gpu, le, case, work, par, want)
+        _, errors = D.SCRUB.check_scrub(gpu, le, case, work, par, want)
     return calls, "\n".join(errors)
 
 

@@ -58,23 +58,23 @@ def test_scrub_grid_caps(gpu, le, oracle, family, measure):
             measure.delenv("LEOEC_SCRUB_GRID")
         else:
             measure.setenv("LEOEC_SCRUB_GRID", grid)
-        for case in D.position_cases(le, oracle, family):
+        for case in D.SCRUB.cases(le, oracle, family):
             dmg, _, locate = S.position_batch(case)
             want = S.two_block_word(oracle, le, case, dmg, locate)
             assert want[-1] == S.MANY  # m = 4: every word by construction
             work, par = L.damaged_arenas(gpu, case, dmg)
             errors += [f"LEOEC_SCRUB_GRID={grid}: {e}"
-                       for e in D.check_scrub(gpu, le, case, work, par, want)[1]]
+                       for e in D.SCRUB.check_scrub(gpu, le, case, work, par, want)[1]]
             dmg, want = D.dense_batch(case)
             work, par = L.damaged_arenas(gpu, case, dmg)
             errors += [f"LEOEC_SCRUB_GRID={grid} dense: {e}"
-                       for e in D.check_scrub(gpu, le, case, work, par, want)[1]]
+                       for e in D.SCRUB.check_scrub(gpu, le, case, work, par, want)[1]]
         # every valid byte of block b damaged in object b: every item's stores are needed
-        for case in D.whole_cases(le, oracle, family):
+        for case in D.SCRUB.whole_cases(le, oracle, family):
             blocks = S.whole_batch(case)
             work, par = S.whole_arenas(gpu, case, blocks)
             errors += [f"LEOEC_SCRUB_GRID={grid} whole blocks: {e}" for e in
-                       D.check_scrub(gpu, le, case, work, par, S.whole_words(case, blocks))[1]]
+                       D.SCRUB.check_scrub(gpu, le, case, work, par, S.whole_words(case, blocks))[1]]
     assert not errors, "\n".join(errors[:20])
 
 

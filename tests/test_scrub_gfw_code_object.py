@@ -16,8 +16,10 @@ import re
 
 import pytest
 
-import scrub_gfw_helpers as X
+import scrub_dev_helpers as D
 import test_locate_ws_code_object as CO
+
+X = D.SCRUB_GFW
 
 CSRC = os.path.join(CO.ROOT, "leo_erasure_amd", "csrc")
 OBJS = {"product": os.path.join(CSRC, "_build", "scrub.o"),
@@ -53,7 +55,7 @@ def test_geometry_constants_are_the_sources():
     assert X.TILE == 64 * 16 * (16 // 4)
     assert re.findall(r"constexpr int kGfwHealWaves = (\d+);", text) == ["4"]
     assert "inline uint32_t gfw_heal_list_resident() { return 4u * (uint32_t)kGfwHealWaves; }" in text
-    assert X.gfw_heal_list_resident() == 4 * 4
+    assert X.resident() == 4 * 4
     # the grid rule: the launcher hands its items and resident() to list_grid
     with open(os.path.join(CSRC, "scrub_gfw_impl.hpp")) as f:
         assert ("const dim3 g(list_grid((uint64_t)a.h.nobj * a.h.tiles, gfw_heal_list_resident(), cap));"

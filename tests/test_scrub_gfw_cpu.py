@@ -27,11 +27,12 @@ import pytest
 import gpu_helpers as H
 import locate_gfw_helpers as G
 import scrub_dev_helpers as D
-import scrub_gfw_helpers as X
 import scrub_helpers as S
 import test_scrub_ws_cpu as TS
 from test_locate_ws_cpu import CID, INVALID
 from test_scrub_cpu import Bufs
+
+X = D.SCRUB_GFW
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "leo_erasure_amd", "csrc")
@@ -157,7 +158,7 @@ def test_argument_errors(le, cfg):
     o, p, r, t, ws = b.objs, b.parity, b.report, b.totals, b.ws
     ostr, pstr = 4096, m * bs
     for nobj in (1, 3, 5):
-        wb = X.head(nobj) + m * bs  # the minimum
+        wb = D.head(nobj) + m * bs  # the minimum
         assert wb <= 8192
 
         def call(objs=o, ostr=ostr, parity=p, pstr=pstr, report=r, totals=t, ws=ws, wb=wb):
@@ -174,13 +175,13 @@ def test_argument_errors(le, cfg):
         # a workspace one byte below the minimum, the header and index words
         # alone, and none
         assert call(wb=wb - 1) == E_ARG
-        assert call(wb=X.head(nobj)) == E_ARG
+        assert call(wb=D.head(nobj)) == E_ARG
         assert call(wb=0) == E_ARG
         # report or totals inside the workspace: at its start, in its index
         # words, in its encode region, at its last word, reaching in from below
         assert call(report=ws) == E_ARG
         assert call(report=ws + 16) == E_ARG
-        assert call(report=ws + X.head(nobj)) == E_ARG
+        assert call(report=ws + D.head(nobj)) == E_ARG
         assert call(report=ws - 4 * nobj + 4) == E_ARG
         assert call(totals=ws) == E_ARG
         assert call(totals=ws + wb - 8) == E_ARG
@@ -203,7 +204,7 @@ def test_argument_errors(le, cfg):
     hbs, _ = le.layout(cls, (k, m, w), huge)
     assert hbs >= 1 << 32
     assert _scrub(le, cid, k, m, w, o, huge, huge, 1, p, m * hbs, r, t, ws,
-                  X.head(1) + m * hbs) == E_BAD_SIZE
+                  D.head(1) + m * hbs) == E_BAD_SIZE
 
 
 def test_workspace_query(le):
@@ -215,7 +216,7 @@ def test_workspace_query(le):
             want = 16 + (4 * nobj + 15) // 16 * 16 + nobj * m * bs
             assert _query(le, cid, k, m, w, size, nobj) == (OK, want), (cls, k, m, w, nobj)
             assert le.device.scrub_gfw_workspace(cls, (k, m, w), size, nobj) == want
-            assert want == X.head(nobj) + le.device.locate_gfw_workspace(cls, (k, m, w), size, nobj)
+            assert want == D.head(nobj) + le.device.locate_gfw_workspace(cls, (k, m, w), size, nobj)
         assert le.lib.leoec_scrub_gfw_dev_workspace(cid, k, m, w, size, 1, None) == E_ARG
         for nobj in (1 << 62, (1 << 64) - 1, 1 << 50):
             assert _query(le, cid, k, m, w, size, nobj)[0] == E_BAD_SIZE

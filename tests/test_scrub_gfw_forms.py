@@ -31,8 +31,9 @@ import pytest
 
 import locate_gfw_helpers as G
 import scrub_dev_helpers as D
-import scrub_gfw_helpers as X
 import scrub_helpers as S
+
+X = D.SCRUB_GFW
 
 FAMILIES = [("vandrs", 20, 4, 8, 8704), ("vandrs", 10, 4, 16, 8704), ("vandrs", 6, 3, 32, 8704)]
 CAP = 7

@@ -14,16 +14,14 @@ import locate_helpers as L
 import locate_ws_helpers as W
 import scrub_dev_helpers as D
 import scrub_helpers as S
-import scrub_ws_helpers as X
 
 FAMILIES = L.FAMILIES + W.FAMILIES
 
 
 def sizes(family):
-    """scrub_dev_helpers.sizes for the fused families, scrub_ws_helpers.cases'
+    """scrub_dev_helpers.SCRUB.sizes for the fused families, SCRUB_WS.sizes'
     three for the bitmatrix ones."""
-    cls, k, m, w, B = family
-    return D.sizes(family) + ([k * B] if S.bitsliced(cls) else [])
+    return (D.SCRUB_WS if S.bitsliced(family[0]) else D.SCRUB).sizes(family)
 
 
 def whole_cases(le, oracle, family):

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import locate_ws_helpers as W
-import scrub_ws_helpers as X
+import scrub_dev_helpers as D
 from test_locate_ws_code_object import TOOLS, _tool, kernel_notes
 from test_locate_ws_cpu import CID, INVALID
 from test_locate_ws_cpu import UNSERVED as LOCATE_WS_UNSERVED
@@ -133,7 +133,7 @@ def test_argument_errors(le, cfg):
     o, p, r, t, ws = b.objs, b.parity, b.report, b.totals, b.ws
     ostr, pstr = 4096, m * bs
     for nobj in (1, 3, 5):
-        wb = X.head(nobj) + m * bs  # the minimum
+        wb = D.head(nobj) + m * bs  # the minimum
         assert wb <= 8192
 
         def call(objs=o, ostr=ostr, parity=p, pstr=pstr, report=r, totals=t, ws=ws, wb=wb):
@@ -151,7 +151,7 @@ def test_argument_errors(le, cfg):
         # words, in its encode region, at its last word, reaching in from below
         assert call(report=ws) == E_ARG
         assert call(report=ws + 16) == E_ARG
-        assert call(report=ws + X.head(nobj)) == E_ARG
+        assert call(report=ws + D.head(nobj)) == E_ARG
         assert call(report=ws - 4 * nobj + 4) == E_ARG
         assert call(totals=ws) == E_ARG
         assert call(totals=ws + wb - 8) == E_ARG
@@ -163,7 +163,7 @@ def test_argument_errors(le, cfg):
         # a workspace one byte below the minimum, the header and index words
         # alone, and none
         assert call(wb=wb - 1) == E_ARG
-        assert call(wb=X.head(nobj)) == E_ARG
+        assert call(wb=D.head(nobj)) == E_ARG
         assert call(wb=0) == E_ARG
         # the batch's own pointers and strides, as check_dev_batch gives them
         assert call(objs=None) == E_ARG
@@ -179,7 +179,7 @@ def test_argument_errors(le, cfg):
     hbs, _ = le.layout(cls, (k, m, w), huge)
     assert hbs >= 1 << 32
     assert _scrub(le, cid, k, m, w, o, huge, huge, 1, p, m * hbs, r, t, ws,
-                  X.head(1) + m * hbs) == E_BAD_SIZE
+                  D.head(1) + m * hbs) == E_BAD_SIZE
 
 
 def test_workspace_query(le):
@@ -194,7 +194,7 @@ def test_workspace_query(le):
             locate = ctypes.c_uint64()
             assert le.lib.leoec_locate_ws_dev_workspace(cid, k, m, w, size, nobj,
                                                         ctypes.byref(locate)) == OK
-            assert want == X.head(nobj) + locate.value
+            assert want == D.head(nobj) + locate.value
         assert le.lib.leoec_scrub_ws_dev_workspace(cid, k, m, w, size, 1, None) == E_ARG
         for nobj in (1 << 62, (1 << 64) - 1, 1 << 50):
             assert _query(le, cid, k, m, w, size, nobj)[0] == E_BAD_SIZE

@@ -13,7 +13,7 @@ wrong on a second trip: state carried over from the previous item (its
 accumulators, which are zeroed per item, its record, its `full`: the position
 batch mixes objects whose lost block is the ragged last data block with
 objects whose blocks are all whole) and a skip not taken by the whole wave.
-The sizes are test_device_scrub_ws.py's three (scrub_ws_helpers.cases): at
+The sizes are test_device_scrub_ws.py's three (scrub_dev_helpers.SCRUB_WS.sizes): at
 k B - 1 and k B a workgroup's successive items alternate between whole tiles
 (the unguarded loads and stores) and a packet's last, partial tile (the guarded
 ones).  The expectations are test_device_scrub_ws.py's, byte for byte.
@@ -34,7 +34,8 @@ import pytest
 import locate_ws_helpers as W
 import scrub_dev_helpers as D
 import scrub_helpers as S
-import scrub_ws_helpers as X
+
+X = D.SCRUB_WS
 
 FAMILIES = [("cauchyrs", 10, 4, 8, 4352 * 8), ("liberation", 4, 2, 7, 2176 * 7),
             ("cauchyrs", 5, 3, 17, 8704 * 17)]

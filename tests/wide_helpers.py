@@ -27,7 +27,6 @@ import locate_helpers as L
 import locate_ws_helpers as W
 import scrub_dev_helpers as D
 import scrub_helpers as S
-import scrub_ws_helpers as X
 import verify_helpers as V
 
 STRIDE = 2**32 + 48     # bytes between rows: kept in 32 bits it becomes 48
@@ -528,9 +527,9 @@ def plan_scrub(le, oracle, case, lay, kind, variant):
                     "workspace tail": WS_TAIL_WANT}
     if kind == "scrub":
         need = le.device.scrub_workspace(case.cls, case.params, case.size, NOBJ)
-        assert need == X.head(NOBJ)
+        assert need == D.head(NOBJ)
     else:
-        need = X.workspace_bytes(le, case, 1 if variant == "min" else None)
+        need = D.SCRUB_WS.workspace_bytes(le, case, 1 if variant == "min" else None)
     words = _words_model(le, oracle, case)
 
     def model(objs):
