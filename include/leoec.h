@@ -134,7 +134,7 @@ int leoec_repair(int coding, int k, int m, int w, const uint8_t *const *blocks, 
  * otherwise LEOEC_E_ARG.  The buffers themselves cannot be checked here:
  * they must hold nobj rows.
  * leoec_encode_dev, leoec_decode_dev, leoec_repair_dev, leoec_update_dev,
- * leoec_verify_dev
+ * leoec_read_dev, leoec_verify_dev
  * (with and without a workspace), the three locate and the three scrub calls
  * (leoec_scrub_gfw_dev serves every class a locate call names one block for,
  * up to k + m = 31) and leoec_heal_dev where it takes one launch (see there:
@@ -361,6 +361,72 @@ int leoec_update_dev(int coding, int k, int m, int w, uint8_t *objs, uint64_t ob
                      uint64_t size, uint64_t nobj, uint8_t *parity, uint64_t parity_stride,
                      const uint8_t *patch, uint64_t patch_stride, uint64_t offset,
                      uint64_t length, void *stream);
+
+/* Read object bytes [offset, offset + length) of every object of a degraded
+ * batch into `out`: the bytes leoec_decode_dev(..., erased, nerased, ...) would
+ * leave in objs, byte for byte, without rebuilding a block.  objs and parity are
+ * never written.  The layout, alignment and stride rules for objs and parity
+ * are leoec_encode_dev's; the range is in object bytes and the same for every
+ * object.
+ * out has the layout of leoec_update_dev's patch: device, 16-byte aligned,
+ * out_stride a multiple of 16 and at least lead + length, lead = offset % 16;
+ * object byte p of object o lands at out[o * out_stride + lead + (p - offset)].
+ * The first lead bytes of a row and the bytes past lead + length are never
+ * written, and what out held before the call never influences the result.
+ * erased[] means what it means to leoec_decode_dev: ids in 0..k+m-1, coding
+ * ids allowed ("not a survivor"), the survivors the first k intact ids
+ * ascending.  The present contents of an erased block, data or coding, are
+ * never read.  Bytes of a survivor data block past `size` are taken as zero and
+ * never dereferenced, as in encode.
+ * Only what the range needs is read.  The range is split at data-block
+ * boundaries:
+ *   - a maximal run of intact data blocks is one launch that copies the
+ *     range's own bytes (they are contiguous in the row);
+ *   - an erased data block j the range meets is rebuilt for the range's bytes
+ *     alone.  vandrs and isars read the 16-byte lanes that hold the range's
+ *     columns in the k survivors, 16 survivors a launch.  cauchyrs and
+ *     liberation read, at the lane positions the segment touches, the survivor
+ *     packets whose column of block j's decode bit-rows meets a touched packet
+ *     of block j, and no other survivor packet; a survivor travels as its id
+ *     and its w column masks, 768 argument words a launch (768 / (w + 1)
+ *     survivors).  With several launches the first stores the bytes and the
+ *     later ones XOR into them, in stream order;
+ *   - an erased data block the range does not meet costs nothing.
+ * About (k + 1) bytes move per byte read from a lost block, 2 per byte of an
+ * intact one.  Nothing is allocated, uploaded or waited for, the coefficients
+ * travel as kernel arguments, so the call can be captured into a graph after
+ * the first plain call of a (code, erased set, lost block): that call inverts
+ * the decode map on the host (the rows are kept in a bounded host cache) and
+ * loads this call's code object.  leoec_gf_init does not cover it, as it does
+ * not cover leoec_update_dev's.  Serves every configuration leoec_decode_dev
+ * serves, k + m > 32 included.
+ * Statuses, in this order, all before the device is opened:
+ * leoec_check_params' for the layout and parameters; the erased list as
+ * leoec_decode_dev checks it (LEOEC_E_ARG for nerased < 0 or a NULL list with
+ * nerased > 0, LEOEC_E_BAD_ID for an id outside 0..k+m-1,
+ * LEOEC_E_NOT_ENOUGH_BLOCKS for fewer than k intact ids); LEOEC_OK with nothing
+ * written for nobj, length or size 0; LEOEC_E_BAD_SIZE when offset + length
+ * exceeds `size` or wraps; the batch checks of objs and parity (LEOEC_E_ARG;
+ * LEOEC_E_BAD_SIZE: a block of 4 GiB or more), then LEOEC_E_ARG for a NULL or
+ * misaligned out, an out_stride that breaks the rule above, or an out extent
+ * ((nobj - 1) * out_stride + lead + length bytes) that overlaps the extent of
+ * objs or parity; then the device.
+ * Against the path without this call (leoec_decode_dev of the batch, then a
+ * device copy of the range), measured on an MI355X with 2,048 objects of 1 MiB
+ * (tools/read_bench.py, profiles/read_bench.txt): a 4 KiB range inside a lost
+ * block takes 0.019-0.093 ms against 0.42-0.49 ms (0.04-0.21 of it) for
+ * vandrs(10,4,8), vandrs(10,4,16), cauchyrs(10,4,8) and liberation(4,2,7).  With
+ * one lost block cauchyrs and liberation win up to the whole object (0.26-0.80
+ * from 64 KiB on), vandrs(10,4,8) up to about 89 KB and vandrs(10,4,16), whose
+ * multiply is the bound, up to about 43 KB.  Every lost block of a range reads
+ * the survivors' columns again: a range of more than about one block that meets
+ * several lost blocks belongs to leoec_decode_dev and a copy (1.5-3.2 times as
+ * long with m lost blocks at 256 KiB and at the whole object; liberation(4,2,7)
+ * still 0.65-0.87). */
+int leoec_read_dev(int coding, int k, int m, int w, const uint8_t *objs, uint64_t obj_stride,
+                   uint64_t size, uint64_t nobj, const uint8_t *parity, uint64_t parity_stride,
+                   const int *erased, int nerased, uint64_t offset, uint64_t length,
+                   uint8_t *out, uint64_t out_stride, void *stream);
 
 /* leoec_locate_dev's word for an object that is inconsistent in a way no
  * single block explains.  The bit lies at or above k + m, so leoec_heal_dev

@@ -49,7 +49,7 @@ EXPORTS = (
     "leoec_locate_gfw_dev_workspace", "leoec_locate_gfw_dev", "leoec_locate_wrows",
     "leoec_scrub_gfw_dev_workspace", "leoec_scrub_gfw_dev", "leoec_scrub_wrows",
     "leoec_heal_ws_dev_workspace", "leoec_heal_ws_dev", "leoec_heal_bitrows", "leoec_heal_wrows",
-    "leoec_update_dev",
+    "leoec_update_dev", "leoec_read_dev",
 )
 
 
@@ -135,6 +135,7 @@ def _load(path=LIB_PATH):
                                                    ctypes.POINTER(ctypes.c_uint32), c_int]
     L.leoec_heal_wrows.argtypes = L.leoec_heal_bitrows.argtypes
     L.leoec_update_dev.argtypes = batch + [vp, u64, u64, u64, vp]
+    L.leoec_read_dev.argtypes = batch + [ctypes.POINTER(c_int), c_int, u64, u64, vp, u64, vp]
     if hasattr(L, "leoec_measure_reload"):
         L.leoec_measure_reload.argtypes = []
         L.leoec_measure_reload.restype = None

@@ -120,6 +120,7 @@ const Knobs* read_env() {
   k->scrub_grid = env_int("LEOEC_SCRUB_GRID", k->scrub_grid);
   k->heal_ws_chunk = env_int("LEOEC_HEAL_WS_CHUNK", k->heal_ws_chunk);
   k->update_chunk = env_int("LEOEC_UPDATE_CHUNK", k->update_chunk);
+  k->read_chunk = env_int("LEOEC_READ_CHUNK", k->read_chunk);
   return k;
 }
 

@@ -136,6 +136,10 @@ struct Knobs {
   int update_chunk = 0;      // LEOEC_UPDATE_CHUNK=n: leoec_update_dev in chunks of at most n objects
                              //   (the chunk seam at test-sized batches; 0: the shipped chunk, which
                              //   only keeps a launch's grid below 2^31)
+  // read.hip
+  int read_chunk = 0;        // LEOEC_READ_CHUNK=n: leoec_read_dev in chunks of at most n objects
+                             //   (the chunk seam at test-sized batches; 0: the shipped chunk, which
+                             //   only keeps a launch's grid below 2^31)
 };
 
 const Knobs& knobs();

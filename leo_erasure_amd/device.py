@@ -467,6 +467,31 @@ def update(coding, params, objs, size, parity, patch, offset, length, nobj=None,
                                     _row_stride(patch), offset, length, _stream(stream)))
 
 
+def read(coding, params, objs, size, parity, erased, offset, length, out=None, nobj=None,
+         stream=None):
+    """leoec_read_dev: object bytes ``[offset, offset + length)`` of every object
+    of a degraded batch, the bytes ``decode(..., erased)`` would leave in
+    ``objs``, without rebuilding a block and without writing ``objs`` or
+    ``parity``.  Returns ``out`` (``[nobj, out_stride]``, allocated as ``nobj``
+    rows of ``round_up(offset % 16 + length, 16)`` bytes when not given): row o
+    starts at the 16-byte lane that holds ``offset``, so object byte p is
+    ``out[o, offset % 16 + (p - offset)]``; no other byte of ``out`` is
+    written."""
+    k, m, w, nobj, _ = _batch(coding, params, objs, size, parity, nobj)
+    if offset < 0 or length < 0:
+        raise ValueError("read: negative offset or length")
+    lead = offset % 16
+    if out is None:
+        out = torch.empty((nobj, (lead + length + 15) // 16 * 16), dtype=torch.uint8,
+                          device=objs.device)
+    _rows(out, nobj, lead + length if length else 0, "out")
+    er = (ctypes.c_int * max(len(erased), 1))(*erased)
+    _lib.check(lib.leoec_read_dev(_cid(coding), k, m, w, objs.data_ptr(), _row_stride(objs), size,
+                                  nobj, parity.data_ptr(), _row_stride(parity), er, len(erased),
+                                  offset, length, out.data_ptr(), _row_stride(out), _stream(stream)))
+    return out
+
+
 def heal_bitrows(coding, params, mask, r):
     """leoec_heal_bitrows (no device needed): the map heal_ws() rebuilds the
     r-th lost id (ascending, from 0) of ``mask`` of a cauchyrs or liberation
